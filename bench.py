@@ -10,17 +10,21 @@ configs[1]: pose_hrnet_w32 256x192, batch 64 per GPU, flip-test on.
 The timed mode (`value`, `dtype`) is the PARITY-GRADE one: split-fp16 storage ("f16x2": 22-bit hi+lo
 operands, three fp16 MFMAs per product, fp32 accumulate), which holds the north-star contract (heat-maps
 within 1e-3 of the fp32 reference, arg-max identical).  The reduced-precision bf16-storage mode that
-configs[1] names is timed right after it and reported under `other_modes` with its own parity block -- it
+configs[1] names is timed right after it (with --full) and reported under `other_modes` with its own parity block -- it
 does NOT meet the contract and is never the headline.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline mode and prints the line.  --dump-outputs DIR
+then also writes what the last timed step computed (see dump_outputs).  --full adds everything else the line
+used to carry: the bf16 and one-lane modes, roofline, whole_step, CPU baseline + parity and the other configs.
 
 With --gpus N > 1 and no torch.distributed environment the script starts N ranks of itself
 (python -m torch.distributed.run, one per GPU) before anything touches the GPU and relays rank 0's line.
 A batch of the split-fp16 mode runs as two sub-batch lanes inside udp_hrnet_forward (two hipGraphs on two streams, joined
 before the flip fuse; include/udp_pose_hip.h: udp_hrnet_lanes) -- still one step = one batch of 64 crops.
 Prints ONE JSON line (rank 0).  `value` is whole-job images/s; multi-GPU is weak scaling over
-independent replicas (every rank decodes its own batch; no data-path collective).  The line also
+independent replicas (every rank decodes its own batch; no data-path collective).  With --full the line also
 carries `roofline` (dominant kernel class: algorithmic FLOPs / measured launch time vs the dense
 MFMA peak, from a hipEvent-instrumented pass of the same K steps) and `cpu_baseline` (the CPU
 oracle -- stock torch fp32 conv graph + NumPy decode, proven equal to the reference in
@@ -299,7 +303,29 @@ def time_mode(dtype, args, device, rank, in_h, in_w, tt, barrier):
     barrier()
     dt = time.perf_counter() - t0
     assert torch.isfinite(out[1]).all()
-    return sd, net, hp, dt
+    return sd, net, hp, dt, out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, hp, out):
+    """What the last timed step handed its caller: keypoints in image space (`preds`), `maxvals`, keypoints in
+    heat-map space (`preds_in`) and the flip-fused heat-maps the decode read (`heatmaps`), as DIR/<name>.npy.
+    Heat-maps that would push the total past 64 MB are cut to a fixed, seeded sample of batch rows (sorted)."""
+    preds, maxvals, pin, _ = out
+    arrays = {"preds": preds, "maxvals": maxvals, "preds_in": pin}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    hm = hp.fused
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values())
+    row_bytes = hm[0].numel() * 4
+    if hm.shape[0] * row_bytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(hm.shape[0], max(0, room // row_bytes), replace=False))
+        hm = hm[torch.from_numpy(rows).to(hm.device)]
+    arrays["heatmaps"] = hm.detach().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():                       # f64 keypoints, f32 maxvals and heat-maps
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def golden_parity(model, dtype, device):
@@ -329,7 +355,7 @@ def time_other_inference(model, args, device):
     a.model, a.batch = model, (32 if model == "w48" else 64)
     _, h, w, _ = MODELS_CFG[model]
     tt = "offset" if model == "rsn18" else "gaussian"
-    sd, net, hp, dt = time_mode("f16x2", a, device, 0, h, w, tt, torch.cuda.synchronize)
+    sd, net, hp, dt, _ = time_mode("f16x2", a, device, 0, h, w, tt, torch.cuda.synchronize)
     ms = dt / a.steps * 1e3
     out = {"workload": "%s %dx%d f16x2 inference, batch=%d, flip-test on, %s decode" % (model, h, w, a.batch, "DARK" if tt == "gaussian" else "offset"),
            "value": round(a.batch * a.steps / dt, 1), "unit": "images/s", "ms_per_step": round(ms, 4), "dtype": "f16x2"}
@@ -426,11 +452,16 @@ def main():
     ap.add_argument("--model", default="w32", choices=sorted(MODELS_CFG), help="w32 256x192 (headline), w48 384x288, rsn18 256x192 + offset head/decode")
     ap.add_argument("--dtype", default="f16x2", choices=["f16x2", "f32", "bf16"],
                     help="storage mode that is timed as `value` (default: the parity-grade split-fp16 mode)")
-    ap.add_argument("--no-other-modes", action="store_true", help="do not time the bf16 mode after the headline one")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="do not time W48 / RSN-18 / the training step after the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: other modes, "
+                    "roofline, whole_step, CPU baseline + parity, other configs (each --no-* below switches one part off)")
+    ap.add_argument("--no-other-modes", action="store_true", help="--full: do not time the bf16 / one-lane modes after the headline one")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline and parity block")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: do not time W48 / RSN-18 / the training step after the headline")
     ap.add_argument("--no-graph", action="store_true", help="eager launches on lane streams instead of hipGraph replay")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -466,13 +497,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    sd, net, hp, dt = time_mode(args.dtype, args, device, rank, in_h, in_w, tt, barrier)
+    sd, net, hp, dt, out = time_mode(args.dtype, args, device, rank, in_h, in_w, tt, barrier)
     dt = max_over_ranks(dt)
     ms_per_step = dt / args.steps * 1e3
     value = world * args.batch * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hp, out)
     other = {}
-    if not args.no_other_modes and args.dtype != "bf16":
-        _, _, hp_b, dt_b = time_mode("bf16", args, device, rank, in_h, in_w, tt, barrier)
+    if args.full and not args.no_other_modes and args.dtype != "bf16":
+        _, _, hp_b, dt_b, _ = time_mode("bf16", args, device, rank, in_h, in_w, tt, barrier)
         dt_b = max_over_ranks(dt_b)
         other["bf16"] = {"value": round(world * args.batch * args.steps / dt_b, 1), "unit": "images/s",
                          "ms_per_step": round(dt_b / args.steps * 1e3, 4),
@@ -480,13 +513,14 @@ def main():
                                  "contract (see parity_vs_cpu_oracle.bf16); reported for BASELINE.json configs[1] only"}
         del hp_b
 
-    if not args.no_other_modes and args.dtype == "f16x2" and int(_lib.lib().udp_hrnet_lanes(net._compiled[(in_h, in_w)][0], args.batch)) > 1:
+    if args.full and not args.no_other_modes and args.dtype == "f16x2" and \
+            int(_lib.lib().udp_hrnet_lanes(net._compiled[(in_h, in_w)][0], args.batch)) > 1:
         # the same mode with the sub-batch lanes off: what the two concurrent chains add (and the configuration the
         # roofline pass below measures)
         saved = os.environ.get("UDP_POSE_LANES")
         os.environ["UDP_POSE_LANES"] = "1"
         try:
-            _, _, hp_1, dt_1 = time_mode(args.dtype, args, device, rank, in_h, in_w, tt, barrier)
+            _, _, hp_1, dt_1, _ = time_mode(args.dtype, args, device, rank, in_h, in_w, tt, barrier)
             dt_1 = max_over_ranks(dt_1)
             other["f16x2_one_lane"] = {"value": round(world * args.batch * args.steps / dt_1, 1), "unit": "images/s",
                                        "ms_per_step": round(dt_1 / args.steps * 1e3, 4),
@@ -513,35 +547,36 @@ def main():
                        "weights": "seeded synthetic, BN stats calibrated (tests/golden/bn_calib_%s_gaussian.npz)" % args.model,
                        "inputs": "8 distinct seeded synthetic crops tiled to the batch + N(0, 0.01^2) noise per image, resident in HBM"}}
     if rank == 0:
-        # the headline numbers are complete at this point: nothing below may keep the line from being printed
-        try:
-            line["roofline"] = roofline(net, hp, max(1, min(args.steps, 5)), args.dtype)
-        except Exception as e:                                      # noqa: BLE001
-            line["roofline"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        flops_per_img = 2 * 2 * net.program(in_h, in_w).macs_per_image()
-        line["whole_step"] = {"tflops": round(flops_per_img * args.batch / (ms_per_step * 1e-3) / 1e12, 2),
-                              "algorithmic_act_gbs": round(2 * net.program(in_h, in_w).activation_elems_per_image() *
-                                                           (2 if args.dtype == "bf16" else 4) * args.batch /
-                                                           (ms_per_step * 1e-3) / 1e9, 1),
-                              "hbm_peak_gbs": PEAK_HBM_GBS}
-        if other:
-            line["other_modes"] = other
-        if world == 1 and not args.no_cpu_baseline and args.model == "w32":
+        if args.full:
+            # the headline numbers are complete at this point: nothing below may keep the line from being printed
             try:
-                cb, x, c, s, ref, ref_hm = cpu_baseline(sd)
-                line["cpu_baseline"] = cb
-                modes = sorted({args.dtype, "f32"} | {m for m in other if m in ("f32", "bf16", "f16x2")})
-                line["parity_vs_cpu_oracle"] = parity(modes, sd, x, c, s, ref, ref_hm, device)
-            except Exception as e:                                  # noqa: BLE001
-                line.setdefault("cpu_baseline", {"error": "%s: %s" % (type(e).__name__, e)})
-                line.setdefault("parity_vs_cpu_oracle", {"error": "%s: %s" % (type(e).__name__, e)})
-        if world == 1 and args.model == "w32" and not args.no_other_configs:
-            del hp, net
-            torch.cuda.empty_cache()
-            try:
-                line["other_configs"] = other_configs(args, device, sd)
-            except Exception as e:                                  # noqa: BLE001
-                line["other_configs"] = {"error": "%s: %s" % (type(e).__name__, e)}
+                line["roofline"] = roofline(net, hp, max(1, min(args.steps, 5)), args.dtype)
+            except Exception as e:                                      # noqa: BLE001
+                line["roofline"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            flops_per_img = 2 * 2 * net.program(in_h, in_w).macs_per_image()
+            line["whole_step"] = {"tflops": round(flops_per_img * args.batch / (ms_per_step * 1e-3) / 1e12, 2),
+                                  "algorithmic_act_gbs": round(2 * net.program(in_h, in_w).activation_elems_per_image() *
+                                                               (2 if args.dtype == "bf16" else 4) * args.batch /
+                                                               (ms_per_step * 1e-3) / 1e9, 1),
+                                  "hbm_peak_gbs": PEAK_HBM_GBS}
+            if other:
+                line["other_modes"] = other
+            if world == 1 and not args.no_cpu_baseline and args.model == "w32":
+                try:
+                    cb, x, c, s, ref, ref_hm = cpu_baseline(sd)
+                    line["cpu_baseline"] = cb
+                    modes = sorted({args.dtype, "f32"} | {m for m in other if m in ("f32", "bf16", "f16x2")})
+                    line["parity_vs_cpu_oracle"] = parity(modes, sd, x, c, s, ref, ref_hm, device)
+                except Exception as e:                                  # noqa: BLE001
+                    line.setdefault("cpu_baseline", {"error": "%s: %s" % (type(e).__name__, e)})
+                    line.setdefault("parity_vs_cpu_oracle", {"error": "%s: %s" % (type(e).__name__, e)})
+            if world == 1 and args.model == "w32" and not args.no_other_configs:
+                del hp, net
+                torch.cuda.empty_cache()
+                try:
+                    line["other_configs"] = other_configs(args, device, sd)
+                except Exception as e:                                  # noqa: BLE001
+                    line["other_configs"] = {"error": "%s: %s" % (type(e).__name__, e)}
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

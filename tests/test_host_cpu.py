@@ -291,6 +291,38 @@ def test_bench_gpus_n_launches_its_own_ranks():
         assert 1 <= (r.stdout + r.stderr).count("bench.py needs a GPU") <= 2
 
 
+def test_bench_dump_outputs_keeps_to_its_budget(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files only, at most 64 MB in all; heat-maps past the budget are cut to
+    a fixed, seeded sample of batch rows (the same rows every run), keypoints and maxvals stay whole."""
+    import importlib.util
+    import types
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    n, j = 400, 51                                       # 400 x 51 x 64 x 48 fp32 heat-maps: 251 MB
+    hp = types.SimpleNamespace(fused=torch.randn(n, j, 64, 48, generator=g))
+    out = (torch.randn(n, j, 2, dtype=torch.float64, generator=g), torch.randn(n, j, 1, generator=g),
+           torch.randn(n, j, 2, dtype=torch.float64, generator=g), None)
+    rows = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), hp, out)
+        got = {f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)}
+        assert sorted(got) == ["heatmaps", "maxvals", "preds", "preds_in"]
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        np.testing.assert_array_equal(got["preds"], out[0].numpy())
+        hm = got["heatmaps"]
+        assert 0 < hm.shape[0] < n and hm.shape[1:] == (j, 64, 48)
+        first = hp.fused[:, 0, 0, 0].numpy()                 # distinct per row: finds the row a dumped map came from
+        idx = [int(np.nonzero(first == hm[k, 0, 0, 0])[0][0]) for k in range(hm.shape[0])]
+        assert idx == sorted(set(idx))
+        np.testing.assert_array_equal(hm, hp.fused.numpy()[idx])
+        rows.append(idx)
+    assert rows[0] == rows[1]
+
+
 def test_f16x2_host_encoding_and_fragment_major_weights():
     """Split-fp16 host helpers (udp-pose_amd/f16x2.py): hi + lo * 2^-11 keeps 22 significant bits over fp16's
     normal range (and degrades gracefully below it); pack_weights_ws puts w[tap][cout][cin] where

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of environment knobs inside ONE GPU session: python tools/ab_env.py [--model w32] "" "UDP_POSE_WS_T=12" "A=1,B=2" ...
-Runs bench.py (headline mode only) once per setting and prints images/s, ms/step and the dominant class's launch time."""
+Runs bench.py --full (headline mode and its roofline only) once per setting and prints images/s, ms/step and the dominant class's launch time."""
 import json
 import os
 import subprocess
@@ -16,8 +16,8 @@ for setting in args or [""]:
     for kv in filter(None, setting.split(",")):
         k, v = kv.split("=", 1)
         env[k] = v
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", model, "--steps", "30", "--warmup", "5", "--no-cpu-baseline",
-                        "--no-other-modes", "--no-other-configs"], env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", model, "--steps", "30", "--warmup", "5", "--full",
+                        "--no-cpu-baseline", "--no-other-modes", "--no-other-configs"], env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])
         rf = d.get("roofline") or {}

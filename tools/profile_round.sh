@@ -14,7 +14,7 @@ stats() {   # name, then the python command line
   cp "$(ls $run/ks_$name/*kernel_stats.csv $run/ks_$name/*/*kernel_stats.csv 2>/dev/null | head -1)" "$out/${tag}_${name}_kernel_stats.csv"
   echo "== $name"; head -6 "$out/${tag}_${name}_kernel_stats.csv" | cut -c1-150
 }
-B="--steps 20 --warmup 5 --no-cpu-baseline --no-other-modes --no-other-configs"
+B="--steps 20 --warmup 5 --full --no-cpu-baseline --no-other-modes --no-other-configs"
 stats bench_${dt} $root/bench.py --dtype $dt $B
 export UDP_POSE_LANES=1
 stats bench_${dt}_onelane $root/bench.py --dtype $dt $B
