@@ -85,8 +85,18 @@ enum udp_op_kind {
   UDP_OP_PSA_SCALE = 8, /* in = x, res = MLP out; out = x * m[c] */
   UDP_OP_BLOCK = 10,    /* fused BasicBlock, bf16, 32 channels: out = relu(conv3x3(relu(conv3x3(in)+b)) + b2 + in);
                            w_off/b_off = first conv, w2_off/b2_off = second conv (pose_hrnet.py:43-59) */
-  UDP_OP_PSA_SP = 9     /* in = theta [C/2] (1x1 conv of the scaled map), res = scaled map [C], up_buf[0] = MLP out;
+  UDP_OP_PSA_SP = 9,    /* in = theta [C/2] (1x1 conv of the scaled map), res = scaled map [C], up_buf[0] = MLP out;
                            out = res * sigmoid(sum_j gbar_j softmax_HW(theta_j)) */
+  /* ConvTranspose2d(k=4, stride=2, pad=1) + folded BatchNorm (+ ReLU): the deconv head of pose_resnet
+   * (deep_hrnet/lib/models/pose_resnet.py:155-193).  ks = 4, stride = 2, hin x win -> hout = 2 hin x wout = 2 win,
+   * UDP_F32 (cin % 16 == 0) and UDP_F16X2 (cin % 32 == 0), cout % 8 == 0, no addends.  Output row 2m+a (a in {0,1})
+   * takes input rows m-1+a+t with ky = 3-a-2t (t in {0,1}), columns alike: phase (a,b) is a 2x2 conv over the 3x3
+   * input window around (m,n), 4*cin*cout MACs per output pixel.  Weights: 16 "taps" pt = 4*(2a+b) + (2t+u) holding
+   * w[ci][co][3-a-2t][3-b-2u] (PyTorch's [cin][cout][kh][kw] with the BatchNorm scale folded along dim 1, the deconv
+   * bias folded into `bias`), laid out as a 16-tap conv: wfmt 0 (UDP_F32) fp32 [pt][cout_pad][cin]; wfmt 1
+   * (UDP_F16X2, required there) the fragment-major blocks described at `wfmt` with tap = pt, scaled by 2^wexp
+   * (udp_pose_amd.f16x2.pack_deconv_weights_ws builds it). */
+  UDP_OP_DECONV = 11
 };
 
 #define UDP_MAX_LANES 4
@@ -125,7 +135,7 @@ typedef struct udp_conv_op {
                               weight-stationary kernel -- 1 KiB blocks [tap][cin chunk of 32][cout pair of 32]
                               [block nb of 16][plane hi|lo], a block = 64 lanes x 8 fp16: lane kg*16 + li holds
                               w[tap][32*pair + 8*(li>>2) + 4*nb + (li&3)][32*chunk + 8*kg .. +7] (cin zero-padded to
-                              a multiple of 32).  The stored numbers are the weights times 2^wexp: plane hi =
+                              a multiple of 32).  UDP_OP_DECONV: the same over its 16 phase/tap pairs (see there).  The stored numbers are the weights times 2^wexp: plane hi =
                               fp16(w * 2^wexp), plane lo = fp16(w * 2^wexp - hi) (the plain residual, NOT scaled by 2^11
                               as activations are).  udp_pose_amd.f16x2.pack_weights_ws builds it. */
   int32_t wexp;            /* wfmt 1: power-of-two scale of the stored weights, chosen so that max |w| * 2^wexp lies in
@@ -188,8 +198,8 @@ int udp_hrnet_num_launches(const udp_hrnet* h);
 double udp_hrnet_flops_per_image(const udp_hrnet* h);
 
 /* One fused conv launch on raw pointers (the operator the program above is made of; used by
- * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV or
- * UDP_OP_FUSE), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
+ * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE or
+ * UDP_OP_DECONV: NHWC in / out, weights as documented there, no res / up), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
  * its buffer ids and blob offsets are ignored except out_buf == UDP_BUF_OUTPUT, which selects
  * the NCHW fp32 output form.  in/res/ups/out: NHWC `dtype`; weights [ks*ks][cout_pad][cin]
  * `dtype`; bias fp32 [cout_pad].  Replaces conv+BN(+add)(+ReLU), pose_hrnet.py:43-59.

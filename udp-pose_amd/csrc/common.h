@@ -131,6 +131,9 @@ int describe_ws_multi(const Launch* members, int n, ConvMulti* m, Launch* out);
 int describe_conv_chain(ConvParams p, Launch* out);   // two 1x1 convs chained through registers (udp_conv_op.chain_cout)
 void ws_set_fill_wgs(long wgs);                       // workgroups a conv launched on its own should reach (tile choice)
 int ws_set_stamps(unsigned long long* dev_buf);      // diagnostic builds (-DUDP_STAMPS) only
+// deconv.hip: ConvTranspose2d(k=4, s=2, p=1) + folded BatchNorm (+ ReLU), UDP_OP_DECONV (fp32 and split fp16)
+int describe_deconv(ConvParams p, int dtype, Launch* out);
+int deconv_h2_overflow(hipStream_t s, int reset, int* flag);
 int conv_h2_overflow(hipStream_t s, int reset, int* flag);       // conv.hip / conv_ws.hip / psa.hip: their g_h2_overflow
 int conv_ws_h2_overflow(hipStream_t s, int reset, int* flag);
 int psa_h2_overflow(hipStream_t s, int reset, int* flag);

@@ -60,7 +60,7 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
   const int nb = (int)h->buf_elems.size();
   auto buf_ok = [&](int b, int64_t need) { return b >= 0 && b < nb && h->buf_elems[b] >= need; };
   const int64_t out_need = (int64_t)o.hout * o.wout * (o.out_pitch ? o.out_pitch : o.cout);
-  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_BLOCK) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_DECONV) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
   if (o.lane < 0 || o.lane >= UDP_MAX_LANES || o.n_wait < 0 || o.n_wait > UDP_MAX_WAIT) return fail(UDP_ERR_ARG, "op %d: lane/n_wait", idx);
   for (int k = 0; k < o.n_wait; ++k)
     if (o.wait_op[k] < 0 || o.wait_op[k] >= idx) return fail(UDP_ERR_ARG, "op %d: wait_op %d must name an earlier op", idx, o.wait_op[k]);
@@ -75,6 +75,27 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
     for (int k = 0; k < 4; ++k)
       if (offs[k] < 0 || (size_t)offs[k] + (k < 2 ? wbytes : 32 * 4) > h->weights_bytes || (offs[k] & 15))
         return fail(UDP_ERR_ARG, "op %d: fused BasicBlock weight/bias range outside the blob or misaligned", idx);
+    return UDP_OK;
+  }
+  if (o.kind == UDP_OP_DECONV) {
+    // ConvTranspose2d(4, 2, 1) + folded BatchNorm (+ ReLU): hin x win -> 2hin x 2win, no addends (deconv.hip)
+    const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
+    const bool h2 = h->dtype == UDP_F16X2;
+    if (h->dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "op %d: deconv: storage modes f32 and f16x2 only", idx);
+    if (o.ks != 4 || o.stride != 2 || o.hin <= 0 || o.win <= 0 || o.hout != 2 * o.hin || o.wout != 2 * o.win || o.cin <= 0 ||
+        o.cin % (h2 ? 32 : 16) || o.cout <= 0 || o.cout % 8 || o.cout_pad < o.cout || o.cout_pad % 32)
+      return fail(UDP_ERR_ARG, "op %d: deconv must be k4 s2 p1, %dx%d -> 2x, cin %% %d == 0, cout %% 8 == 0", idx, o.hin, o.win, h2 ? 32 : 16);
+    if (o.wfmt != (h2 ? 1 : 0)) return fail(UDP_ERR_ARG, "op %d: deconv weights: wfmt %d (f16x2: 1, f32: 0)", idx, o.wfmt);
+    if (o.res_buf != UDP_BUF_NONE || o.n_up || o.n_out2 || o.chain_cout || o.group || o.in_stuff2)
+      return fail(UDP_ERR_UNSUPPORTED, "op %d: deconv takes no addends, second outputs, chains or groups", idx);
+    if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
+      return fail(UDP_ERR_ARG, "op %d: deconv channel views", idx);
+    if (!buf_ok(o.in_buf, (int64_t)o.hin * o.win * ipitch) || !buf_ok(o.out_buf, out_need) || o.in_buf == o.out_buf)
+      return fail(UDP_ERR_ARG, "op %d: deconv buffers missing, too small or aliased", idx);
+    const size_t wbytes = h2 ? (size_t)16 * (o.cin / 32) * (o.cout_pad / 32) * 4096 : (size_t)16 * o.cout_pad * o.cin * 4;
+    if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15) || o.b_off < 0 ||
+        (size_t)o.b_off + (size_t)o.cout_pad * 4 > h->weights_bytes || (o.b_off & 15) || o.wexp < -40 || o.wexp > 40)
+      return fail(UDP_ERR_ARG, "op %d: deconv weight / bias range outside the blob or misaligned", idx);
     return UDP_OK;
   }
   if (o.kind >= UDP_OP_PSA_POOL) {
@@ -190,6 +211,7 @@ extern "C" int udp_f16x2_overflow(void* stream, int reset) {
   int rc = conv_h2_overflow(s, reset, &flag);
   if (!rc) rc = conv_ws_h2_overflow(s, reset, &flag);
   if (!rc) rc = psa_h2_overflow(s, reset, &flag);
+  if (!rc) rc = deconv_h2_overflow(s, reset, &flag);
   return rc ? rc : flag;
 }
 
@@ -231,6 +253,7 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
     if (ops[i].kind == UDP_OP_STEM || ops[i].kind == UDP_OP_STEM7 || ops[i].kind == UDP_OP_CONV)
       h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;
     if (ops[i].kind == UDP_OP_BLOCK) h->flops += 2 * 2.0 * 9 * 32 * 32 * ops[i].hout * ops[i].wout;
+    if (ops[i].kind == UDP_OP_DECONV) h->flops += 2.0 * 4 * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;   // 2x2 taps per output pixel
     if (ops[i].kind == UDP_OP_CONV && ops[i].chain_cout) h->flops += 2.0 * ops[i].cout * ops[i].chain_cout * ops[i].hout * ops[i].wout;
     h->ops.push_back(ops[i]);
   }
@@ -341,7 +364,7 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       p.add2_coff[k] = o.add2_coff[k];
       p.add2_pitch[k] = o.add2_pitch[k] ? o.add2_pitch[k] : o.cout;
     }
-    if (is_stem || o.kind == UDP_OP_CONV) {
+    if (is_stem || o.kind == UDP_OP_CONV || o.kind == UDP_OP_DECONV) {
       p.wgt = h->weights + o.w_off;
       p.bias = reinterpret_cast<const float*>(h->weights + o.b_off);
     }
@@ -374,6 +397,7 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       case UDP_OP_FUSE: rc = describe_fuse(p, h->dtype, &ls[i]); break;
       case UDP_OP_MAXPOOL: rc = describe_maxpool(p, h->dtype, &ls[i]); break;
       case UDP_OP_BILINEAR: rc = describe_bilinear(p, h->dtype, &ls[i]); break;
+      case UDP_OP_DECONV: rc = describe_deconv(p, h->dtype, &ls[i]); break;
       default:
         if (o.chain_cout) {
           rc = describe_conv_chain(p, &ls[i]);
@@ -708,8 +732,13 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (!o || !in || !out) return fail(UDP_ERR_ARG, "udp_conv2d_fused: null pointer");
   if (dtype != UDP_F32 && dtype != UDP_BF16 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "udp_conv2d_fused: dtype %d", dtype);
   if (n <= 0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: n=%d", n);
-  if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE) return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
-  if (o->kind == UDP_OP_CONV && (!weights || !bias)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV) return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
+  if (o->kind != UDP_OP_FUSE && (!weights || !bias)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind == UDP_OP_DECONV) {
+    if (o->ks != 4 || o->stride != 2 || o->hout != 2 * o->hin || o->wout != 2 * o->win)
+      return fail(UDP_ERR_ARG, "udp_conv2d_fused: deconv must be k4 s2 p1 (output = 2x the input)");
+    if (res || o->n_up || o->out_buf == UDP_BUF_OUTPUT) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused: deconv takes no addends and writes NHWC");
+  }
   if (o->cout <= 0 || o->cout_pad < o->cout || o->cout_pad % 32 || o->n_up < 0 || o->n_up > 3)
     return fail(UDP_ERR_ARG, "udp_conv2d_fused: bad cout/cout_pad/n_up");
   if (o->kind == UDP_OP_CONV) {
@@ -768,7 +797,9 @@ static int conv2d_fused_impl(const udp_conv_op* o, int dtype, int n, const void*
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Launch l;
   p.bn_ws = bn_ws;
-  const int rc = o->kind == UDP_OP_FUSE ? describe_fuse(p, dtype, &l) : describe_conv(p, dtype, o->ks, o->stride, &l);
+  const int rc = o->kind == UDP_OP_FUSE     ? describe_fuse(p, dtype, &l)
+                 : o->kind == UDP_OP_DECONV ? describe_deconv(p, dtype, &l)
+                                            : describe_conv(p, dtype, o->ks, o->stride, &l);
   if (rc) return rc;
   if (bn_ws) {
     // one partial row of 2*Cout doubles per tile (grid.x); the caller's workspace must hold them

@@ -56,3 +56,28 @@ def pack_weights_ws(wp):
     pl = pl.reshape(2, taps, cp // 32, 4, 2, 4, nch, 4, 8)      # cout = 32*pair + 8*a + 4*nb + b; k = 32*c + 8*kg + j
     out = pl.permute(1, 6, 2, 4, 0, 7, 3, 5, 8).contiguous()    # tap, c, pair, nb, plane, kg, a, b, j  (lane = kg*16 + a*4 + b)
     return out.view(torch.uint8).reshape(-1), wexp
+
+
+def deconv_phase_taps(w, cout_pad=None):
+    """ConvTranspose2d(k=4, s=2, p=1) weight ``[cin, cout, 4, 4]`` -> ``[16][cout_pad][cin]``: the 16 (phase, tap)
+    pairs of UDP_OP_DECONV (include/udp_pose_hip.h) as the taps of a conv -- entry ``4 * (2a + b) + (2t + u)`` holds
+    ``w[:, :, 3 - a - 2t, 3 - b - 2u].T`` (output phase (a, b), input offset (a + t, b + u) in the 3x3 window around
+    the source pixel); cout zero-padded to ``cout_pad`` (default: the next multiple of 32)."""
+    cin, cout, kh, kw = w.shape
+    if (kh, kw) != (4, 4):
+        raise ValueError("deconv kernel %dx%d: only 4x4 (stride 2, pad 1) is supported" % (kh, kw))
+    cout_pad = cout_pad or (cout + 31) // 32 * 32
+    wp = torch.zeros(16, cout_pad, cin, dtype=torch.float32)
+    for a in range(2):
+        for b in range(2):
+            for t in range(2):
+                for u in range(2):
+                    wp[4 * (2 * a + b) + 2 * t + u, :cout] = w[:, :, 3 - a - 2 * t, 3 - b - 2 * u].t().to(torch.float32)
+    return wp
+
+
+def pack_deconv_weights_ws(w, cout_pad=None):
+    """ConvTranspose2d(k=4, s=2, p=1) weight ``[cin, cout, 4, 4]`` (BatchNorm folded) -> ``(bytes, wexp)`` in the
+    fragment-major split-fp16 layout of ``udp_conv_op.wfmt == 1`` over the 16 (phase, tap) pairs of
+    ``deconv_phase_taps`` (UDP_OP_DECONV in UDP_F16X2 storage)."""
+    return pack_weights_ws(deconv_phase_taps(w, cout_pad))

@@ -344,4 +344,68 @@ def get_pose_net_psa(cfg, is_train, **kwargs):
     return get_pose_net(cfg, is_train, psa=True, **kwargs)
 
 
-MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa}
+class PoseResNetHip(PoseHighResolutionNetHip):
+    """pose_resnet / SimpleBaseline (deep_hrnet/lib/models/pose_resnet.py:105-273: ResNet-50 / 101 / 152, three
+    ConvTranspose2d(4, 2, 1) + BN + ReLU, ``final_layer``) inference through the same C ABI; ``state_dict`` in the
+    reference module's key format.  Storage modes "f32" and "f16x2" (the deconv kernel has no bf16 form)."""
+
+    DTYPES = ("f32", "f16x2")
+
+    def __init__(self, cfg, dtype="f32"):
+        from .resnet_plan import pose_resnet_spec
+        if dtype not in self.DTYPES:
+            raise ValueError("pose_resnet: dtype %r is not supported; supported modes: %s" % (dtype, ", ".join(self.DTYPES)))
+        self.cfg = cfg
+        self.extra = _get(cfg, "MODEL", "EXTRA")
+        self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
+        self.spec = pose_resnet_spec(self.extra)          # NotImplementedError for depths / kernels without a kernel
+        self.dtype = dtype
+        self.psa = False
+        self.training, self._trainer, self._stale, self._seen_version = False, None, False, 0
+        self.device = None
+        self.use_graph = True
+        self.max_images_per_launch = None     # None: only the 2 GiB-per-tensor limit of one launch applies
+        self._sd = None
+        self._compiled = {}
+        self._ws = None
+        self._io = {}
+
+    def param_shapes(self):
+        from .synth_resnet import pose_resnet_param_shapes
+        sp = self.spec
+        return pose_resnet_param_shapes(layers=sp["layers"], num_joints=self.num_joints, deconv_filters=sp["deconv_filters"],
+                                        deconv_kernel=4, final_kernel=sp["final_kernel"],
+                                        deconv_with_bias=sp["deconv_with_bias"])
+
+    def load_state_dict(self, state_dict, strict=True):
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        want = self.param_shapes()
+        missing = [k for k in want if k not in sd and not k.endswith("num_batches_tracked")]
+        unexpected = [k for k in sd if k not in want]
+        if missing or (strict and unexpected):
+            raise RuntimeError("state_dict mismatch: missing %s unexpected %s" % (missing[:5], unexpected[:5]))
+        for k, shape in want.items():
+            if k in sd and tuple(sd[k].shape) != tuple(shape):
+                raise RuntimeError("size mismatch for %s: %s vs %s" % (k, tuple(sd[k].shape), tuple(shape)))
+        self._sd = sd
+        self._release()
+        return self
+
+    def init_weights(self, pretrained=""):
+        raise NotImplementedError("pose_resnet: training (and its weight initialisation) is out of scope; load a state_dict")
+
+    def trainer(self):
+        raise NotImplementedError("pose_resnet: the training step covers pose_hrnet only")
+
+    def _make_program(self, h, w):
+        from .resnet_plan import PoseResNetProgram
+        return PoseResNetProgram(self._sd, self.spec, h, w, self.dtype)
+
+
+def get_pose_net_resnet(cfg, is_train, **kwargs):
+    """pose_resnet.py:263-273 (``get_pose_net``): the model for MODEL.EXTRA.NUM_LAYERS; inference only -- the weights
+    come from ``load_state_dict`` (training, hence ``init_weights`` under is_train, is out of scope)."""
+    return PoseResNetHip(cfg, **kwargs)
+
+
+MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet}

@@ -1,0 +1,153 @@
+"""Host compiler for pose_resnet / SimpleBaseline (deep_hrnet/lib/models/pose_resnet.py:105-273) -> the fused op program.
+
+Graph restated from the reference: 7x7 s2 conv + BN + ReLU and a 3x3 s2 max-pool (:112-116, :195-199), four stages
+of Bottlenecks (:64-100, :138-153: the stride sits on the 3x3 conv, the projection shortcut is a 1x1 conv + BN), then
+NUM_DECONV_LAYERS x [ConvTranspose2d(k=4, s=2, p=1) + BN + ReLU] (:155-193) and the 1x1 / 3x3 ``final_layer`` with
+bias (:128-136) writing the NCHW fp32 heat-maps.  ``conv3 + bn3 + shortcut + ReLU`` of a Bottleneck is one conv with
+the residual in its epilogue; every deconv layer is one UDP_OP_DECONV launch (csrc/deconv.hip).
+"""
+from . import _lib
+from .hrnet_plan import BN_EPS, HRNetProgram, _round_up, encode_weights
+
+import torch
+
+# resnet_spec of pose_resnet.py:254-260 (Bottleneck depths only; BasicBlock 18 / 34 ship in no YAML)
+RESNET_LAYERS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+
+
+def _get(cfg, key, default=None):
+    if isinstance(cfg, dict):
+        return cfg.get(key, default)
+    return getattr(cfg, key, default)
+
+
+def pose_resnet_spec(extra):
+    """MODEL.EXTRA of a pose_resnet YAML -> dict(layers, deconv_filters, final_kernel, deconv_with_bias).  Raises
+    NotImplementedError for what the kernels do not cover: BasicBlock depths (18 / 34), deconv kernels other than 4,
+    a deconv count other than 3 (the heat-maps must come out at 1/4 of the input), a final kernel other than 1 / 3."""
+    num_layers = int(_get(extra, "NUM_LAYERS"))
+    if num_layers not in RESNET_LAYERS:
+        raise NotImplementedError("pose_resnet NUM_LAYERS=%d: only the Bottleneck depths %s are supported (BasicBlock "
+                                  "ResNet-18 / 34 ships in no reference YAML)" % (num_layers, sorted(RESNET_LAYERS)))
+    nd = int(_get(extra, "NUM_DECONV_LAYERS", 3))
+    filters = [int(f) for f in _get(extra, "NUM_DECONV_FILTERS", [256] * nd)]
+    kernels = [int(k) for k in _get(extra, "NUM_DECONV_KERNELS", [4] * nd)]
+    if nd != 3 or len(filters) != nd or len(kernels) != nd:
+        raise NotImplementedError("pose_resnet: NUM_DECONV_LAYERS=%d (filters %s, kernels %s): only 3 deconv layers "
+                                  "(heat-maps at 1/4 of the input) are supported" % (nd, filters, kernels))
+    if any(k != 4 for k in kernels):
+        raise NotImplementedError("pose_resnet: NUM_DECONV_KERNELS=%s: only ConvTranspose2d(k=4, s=2, p=1) has a kernel "
+                                  "(kernels 2 / 3 ship in no reference YAML)" % (kernels,))
+    final_kernel = int(_get(extra, "FINAL_CONV_KERNEL", 1))
+    if final_kernel not in (1, 3):
+        raise NotImplementedError("pose_resnet: FINAL_CONV_KERNEL=%d (1 or 3)" % final_kernel)
+    return dict(layers=RESNET_LAYERS[num_layers], deconv_filters=tuple(filters), final_kernel=final_kernel,
+                deconv_with_bias=bool(_get(extra, "DECONV_WITH_BIAS", False)))
+
+
+class _Tracked(dict):
+    """The state_dict, remembering which keys the planner read (tests check that every one is consumed)."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.used = set()
+
+    def __getitem__(self, k):
+        self.used.add(k)
+        return super().__getitem__(k)
+
+    def get(self, k, default=None):
+        if k in self:
+            self.used.add(k)
+        return super().get(k, default)
+
+
+class PoseResNetProgram(HRNetProgram):
+    def __init__(self, state_dict, spec, in_h, in_w, dtype="f32"):
+        if dtype not in ("f32", "f16x2"):
+            raise ValueError("pose_resnet: dtype %r; supported storage modes are 'f32' and 'f16x2' (the deconv kernel "
+                             "has no bf16 form)" % (dtype,))
+        self.spec = spec
+        super().__init__(state_dict, {}, in_h, in_w, dtype)
+
+    @property
+    def consumed_keys(self):
+        return set(self.sd.used)
+
+    def _op(self, kind, x, out, name, **kw):
+        op = dict(kind=kind, ks=kw.pop("ks", 1), stride=kw.pop("stride", 1), relu=int(kw.pop("relu", 0)), cin=x.c,
+                  cout=out.c, cout_pad=_round_up(out.c, 32), hin=x.h, win=x.w, hout=out.h, wout=out.w, inp=x, out=out,
+                  res=None, ups=[], w_off=0, b_off=0, name=name)
+        op.update(kw)
+        self._ops.append(op)
+
+    def _deconv(self, x, d):
+        """deconv_layers[3d] (ConvTranspose2d, [cin, cout, 4, 4], bias if DECONV_WITH_BIAS) + [3d+1] (BatchNorm) + ReLU:
+        the BatchNorm scale folds along dim 1 (the output channels), the deconv bias into the BatchNorm bias."""
+        sd = self.sd
+        q, bn = "deconv_layers.%d" % (3 * d), "deconv_layers.%d" % (3 * d + 1)
+        w = sd[q + ".weight"].detach().to(torch.float64).cpu()
+        cin, cout = int(w.shape[0]), int(w.shape[1])
+        if cin != x.c:
+            raise ValueError("%s expects %d input channels, got %d" % (q, cin, x.c))
+        bias = sd.get(q + ".bias")
+        b = bias.detach().to(torch.float64).cpu() if bias is not None else torch.zeros(cout, dtype=torch.float64)
+        s = sd[bn + ".weight"].detach().to(torch.float64).cpu() / torch.sqrt(
+            sd[bn + ".running_var"].detach().to(torch.float64).cpu() + BN_EPS)
+        w = (w * s[None, :, None, None]).to(torch.float32)
+        b = ((b - sd[bn + ".running_mean"].detach().to(torch.float64).cpu()) * s
+             + sd[bn + ".bias"].detach().to(torch.float64).cpu()).to(torch.float32)
+        cout_pad = _round_up(cout, 32)
+        from .f16x2 import deconv_phase_taps, pack_deconv_weights_ws
+        wexp = 0
+        if self.dtype == "f16x2":
+            packed, wexp = pack_deconv_weights_ws(w, cout_pad)
+            w_off = self._put(packed.numpy().tobytes())
+        else:
+            w_off = self._put(encode_weights(deconv_phase_taps(w, cout_pad), self.dtype))
+        bp = torch.zeros(cout_pad, dtype=torch.float32)
+        bp[:cout] = b
+        out = self._new(cout, 2 * x.h, 2 * x.w)
+        self._op(_lib.UDP_OP_DECONV, x, out, q, ks=4, stride=2, relu=1, cout_pad=cout_pad, w_off=w_off,
+                 b_off=self._put(bp.numpy().tobytes()), wfmt=int(self.dtype == "f16x2"), wexp=wexp)
+        return out
+
+    def _build(self):
+        self.sd = _Tracked(self.sd)
+        sd = self.sd
+        H, W = self.in_h, self.in_w
+        w, b = self._fold("conv1", "bn1")
+        if tuple(w.shape) != (64, 3, 7, 7):
+            raise ValueError("conv1.weight must be [64,3,7,7]")
+        w_off = self._put(w.permute(2, 3, 1, 0).contiguous().numpy().tobytes())     # [ky][kx][ci][cout]
+        b_off = self._put(b.numpy().tobytes())
+        x = self._new(64, H // 2, W // 2)
+        self._ops.append(dict(kind=_lib.UDP_OP_STEM7, ks=7, stride=2, relu=1, cin=3, cout=64, cout_pad=64, hin=H, win=W,
+                              hout=H // 2, wout=W // 2, inp=None, out=x, res=None, ups=[], w_off=w_off, b_off=b_off,
+                              name="conv1"))
+        pooled = self._new(64, H // 4, W // 4)
+        self._op(_lib.UDP_OP_MAXPOOL, x, pooled, "maxpool", ks=3, stride=2)
+        x = pooled
+        for li, nblk in enumerate(self.spec["layers"], start=1):          # _make_layer (:138-153)
+            for k in range(nblk):
+                p = "layer%d.%d" % (li, k)
+                stride = 2 if (li > 1 and k == 0) else 1
+                a = self._conv(x, p + ".conv1", p + ".bn1")
+                t = self._conv(a, p + ".conv2", p + ".bn2", stride=stride)
+                r = x
+                if (p + ".downsample.0.weight") in sd:
+                    r = self._conv(x, p + ".downsample.0", p + ".downsample.1", stride=stride, relu=False)
+                x = self._conv(t, p + ".conv3", p + ".bn3", res=r)       # relu(bn3(conv3(t)) + shortcut)
+        for d in range(len(self.spec["deconv_filters"])):
+            x = self._deconv(x, d)
+        if (x.h, x.w) != (H // 4, W // 4):
+            raise ValueError("pose_resnet: heat-maps at %dx%d, expected %dx%d" % (x.h, x.w, H // 4, W // 4))
+        self._conv(x, "final_layer", None, relu=False, to_output=True)
+        self.out_channels = self._ops[-1]["cout"]
+        for k in sd:
+            if k.endswith("num_batches_tracked"):
+                sd.used.add(k)                                              # BatchNorm bookkeeping, not an operand
+
+    def macs_per_image(self):
+        deconv = sum(4 * op["cin"] * op["cout"] * op["hout"] * op["wout"] for op in self._ops if op["kind"] == _lib.UDP_OP_DECONV)
+        return super().macs_per_image() + deconv
