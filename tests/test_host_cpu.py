@@ -123,11 +123,53 @@ def test_yaml_config_defaults(tmp_path):
     assert cfg["MODEL"]["EXTRA"]["FINAL_CONV_KERNEL"] == 1 and cfg.MODEL.NUM_JOINTS == 17
 
 
+def _slice_writers_share_a_lane(prog):
+    """The buffer assignment tracks only the last writer of a tensor that several ops write in slices (the concat
+    tensors of layer 1, of the exchange units and of the RSN bottlenecks): its consumers are ordered after the earlier
+    writers by the lane's stream alone, so all writers of one tensor must sit on one lane.  Returns how many tensors
+    were walked."""
+    writers = {}
+    for op in prog._ops:
+        if op["out"] is not None:
+            writers.setdefault(op["out"].id, []).append(op)
+    multi = {t: w for t, w in writers.items() if len(w) > 1}
+    for t, w in multi.items():
+        assert len({op["lane"] for op in w}) == 1, "tensor %d: slice writers %s on lanes %s" % (
+            t, [op["name"] for op in w], [op["lane"] for op in w])
+        assert sum(op["cout"] for op in w) <= w[0]["out"].c
+    return len(multi)
+
+
+def test_slice_writers_on_different_lanes_are_refused():
+    """_assign_buffers checks the condition above instead of assuming it: a program whose second slice writer claims
+    another resolution level (hence another lane) is refused."""
+    from udp_pose_amd import program
+
+    class TwoLanes(program.Program):
+        def _build(self):
+            x = self._new(64, self.in_h // 2, self.in_w // 2)
+            cat = self._new(64, self.in_h // 4, self.in_w // 4)
+            self._emit(_lib.UDP_OP_STEM, "stem", None, x, ks=3, stride=2)
+            self._emit(_lib.UDP_OP_CONV, "lo", x, cat, stride=2, cout=32, out_pitch=64)
+            self._emit(_lib.UDP_OP_CONV, "hi", x, cat, stride=2, cout=32, out_coff=32, out_pitch=64, hout=self.hi_rows)
+            self.out_channels = 0
+
+    TwoLanes.hi_rows = 16
+    assert _slice_writers_share_a_lane(TwoLanes({}, 64, 64)) == 1
+    TwoLanes.hi_rows = 8                                   # one level down: lane 1, its fellow writer on lane 0
+    with pytest.raises(RuntimeError, match="different lanes"):
+        TwoLanes({}, 64, 64)
+
+
 def test_lanes_order_every_buffer_hazard():
     """Branch lanes may overlap on the GPU: every RAW / WAR / WAW pair on a physical buffer must be
     ordered by (previous op on the same lane) + (the op's cross-lane wait list), transitively."""
     sd = synth.synth_state_dict(synth.W32_EXTRA, 17, "gaussian", seed=0)
-    ops = hrnet_plan.HRNetProgram(sd, synth.W32_EXTRA, 256, 192, "bf16").ops_array()
+    progs = {d: hrnet_plan.HRNetProgram(sd, synth.W32_EXTRA, 256, 192, d) for d in ("f32", "bf16", "f16x2")}
+    # layer 1's [t | x] tensor in every mode; the block-major modes add one concat tensor per exchange-unit output
+    # i >= 2: one in each of stage 3's four modules, two in each of stage 4's first two (its last has output 0 only)
+    assert {d: _slice_writers_share_a_lane(p) for d, p in progs.items()} == {"f32": 1, "bf16": 1 + 4 + 4, "f16x2": 1 + 4 + 4}
+    ops = progs["bf16"].ops_array()
     n = len(ops)
     hb = [0] * n                      # bitset of ops that happen before op i
     last = {}
@@ -163,6 +205,8 @@ def test_rsn_program_second_outputs_keep_every_hazard_ordered():
     their addends included -- is ordered by lane order + wait lists."""
     from udp_pose_amd import rsn_plan
     sd = synth.synth_rsn18_state_dict(51, seed=4)
+    for dtype in ("f32", "bf16", "f16x2"):
+        assert _slice_writers_share_a_lane(rsn_plan.RSNProgram(sd, 256, 192, dtype)) == 8     # one concat tensor per bottleneck
     prog = rsn_plan.RSNProgram(sd, 256, 192, "f16x2")
     ops = prog.ops_array()
     n = len(ops)

@@ -1,4 +1,5 @@
-"""Host-side compiler: reference YAML (MODEL.EXTRA) + state_dict -> fused op program.
+"""Host-side compiler for HRNet / HRNet-PSA: reference YAML (MODEL.EXTRA) + state_dict -> fused op program
+(program.Program: the op records, the weight blob and the buffer assignment are built there).
 
 Walks the same graph as PoseHighResolutionNet.forward
 (deep_hrnet/lib/models/pose_hrnet.py:436-471; modules :260-273, fuse layers
@@ -7,210 +8,29 @@ emits one ``udp_conv_op`` (include/udp_pose_hip.h) per fused launch:
 
     out = act( conv(in) + bias [+ res] [+ sum_k nearest_up(up_k)] )
 
-* BatchNorm(eval) is folded into the conv: w' = w * gamma/sqrt(var+eps),
-  b' = beta - mean*gamma/sqrt(var+eps), computed in fp64, stored fp32 / bf16.
 * An exchange-unit output y_i = ReLU(sum_j f_ij(x_j)) (:267-272) becomes: the
   1x1 convs of the j>i terms write low-resolution temporaries; the last 3x3
   stride-2 conv of each j<i chain adds the running sum (identity term, the
   upsampled temporaries, earlier chains) in its epilogue, the final one applies
   the ReLU; output 0 has no conv term and is one element-wise launch (or, in the
   last stage-4 module, the epilogue of its 1x1 C->4C conv, :213-221).
-* Activation buffers are assigned by a linear scan over tensor lifetimes.
 """
 import os
 
-import numpy as np
 import torch
 
 from . import _lib
-
-BN_EPS = 1e-5
-
-
-class _T:
-    """An activation tensor (NHWC, per image) in SSA form."""
-    __slots__ = ("id", "c", "h", "w")
-
-    def __init__(self, i, c, h, w):
-        self.id, self.c, self.h, self.w = i, c, h, w
-
-    @property
-    def elems(self):
-        return self.c * self.h * self.w
+from .program import BN_EPS, DTYPES, Program, _T, _V, _round_up, encode_weights, storage_bytes  # noqa: F401 (re-exported)
 
 
-class _V:
-    """Channels [coff, coff + c) of tensor ``t`` (a channel-slice view: udp_conv_op.in_coff / res_coff + pitch)."""
-    __slots__ = ("t", "coff", "c")
-
-    def __init__(self, t, coff, c):
-        self.t, self.coff, self.c = t, coff, c
-
-    @property
-    def h(self):
-        return self.t.h
-
-    @property
-    def w(self):
-        return self.t.w
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
-
-
-DTYPES = ("f32", "bf16", "f16x2")
-F16X2_LO_SCALE = 2048.0          # csrc/conv.hip kLoScale
-
-
-def encode_weights(wp, dtype):
-    """[taps][cout_pad][cin] fp32 -> bytes in the storage dtype.  f16x2: rows of [cin hi][cin lo] fp16 with
-    w ~= hi + lo * 2^-11 (include/udp_pose_hip.h, UDP_F16X2); a folded weight beyond fp16's range is refused."""
-    if dtype == "bf16":
-        return wp.to(torch.bfloat16).contiguous().view(torch.uint8).numpy().tobytes()
-    if dtype == "f16x2":
-        if wp.numel() and float(wp.abs().max()) >= 32768.0:
-            raise ValueError("f16x2 storage: a BatchNorm-folded weight of magnitude %g exceeds the fp16 range"
-                             % float(wp.abs().max()))
-        hi = wp.to(torch.float16)
-        lo = ((wp - hi.to(torch.float32)) * F16X2_LO_SCALE).to(torch.float16)
-        return torch.stack([hi, lo], dim=2).contiguous().view(torch.uint8).numpy().tobytes()
-    return wp.contiguous().numpy().tobytes()
-
-
-def storage_bytes(dtype):
-    """Bytes per stored activation / weight element."""
-    return 2 if dtype == "bf16" else 4
-
-
-class HRNetProgram:
-    """The compiled program: ops (ctypes array), buffer sizes, packed weights."""
-
+class HRNetProgram(Program):
     def __init__(self, state_dict, extra, in_h, in_w, dtype="f32"):
-        if dtype not in DTYPES:
-            raise ValueError("dtype must be one of %s" % (DTYPES,))
-        if in_h % 32 or in_w % 32:
-            raise ValueError("input %dx%d must be a multiple of 32" % (in_h, in_w))
-        self.sd = {k[7:] if k.startswith("module.") else k: v for k, v in state_dict.items()}
         self.extra = extra
-        self.dtype = dtype
-        self.in_h, self.in_w = in_h, in_w
         self.fuse_blocks = os.environ.get("UDP_POSE_NO_BLOCK_FUSION") is None
         self.block_major = dtype in ("bf16", "f16x2")       # modules emitted block by block over all branches
         self.group_convs = self.block_major and os.environ.get("UDP_POSE_NO_GROUPS") is None
-        # split-fp16 convs on the weight-stationary kernel (fragment-major weights, udp_conv_op.wfmt = 1)
-        # (UDP_POSE_WS=0: the LDS-staged conv_mfma_kernel<H2> instead -- A/B knob)
-        self.use_ws = dtype == "f16x2" and os.environ.get("UDP_POSE_WS", "1") != "0"
         self._groups = 0
-        self._tensors = []
-        self._ops = []          # dicts with _T references
-        self._blob = []         # list of (offset, np.ndarray uint8)
-        self._blob_size = 0
-        self._build()
-        self._assign_buffers()
-
-    # ------------------------------------------------------------------ weights
-    def _put(self, arr_bytes):
-        off = _round_up(self._blob_size, 256)
-        self._blob.append((off, arr_bytes))
-        self._blob_size = off + len(arr_bytes)
-        return off
-
-    def _fold(self, conv, bn):
-        w = self.sd[conv + ".weight"].detach().to(torch.float64).cpu()
-        cout = w.shape[0]
-        bias = self.sd.get(conv + ".bias")
-        b = bias.detach().to(torch.float64).cpu() if bias is not None else torch.zeros(cout, dtype=torch.float64)
-        if bn is not None:
-            g = self.sd[bn + ".weight"].detach().to(torch.float64).cpu()
-            beta = self.sd[bn + ".bias"].detach().to(torch.float64).cpu()
-            mean = self.sd[bn + ".running_mean"].detach().to(torch.float64).cpu()
-            var = self.sd[bn + ".running_var"].detach().to(torch.float64).cpu()
-            s = g / torch.sqrt(var + BN_EPS)
-            w = w * s[:, None, None, None]
-            b = (b - mean) * s + beta
-        return w.to(torch.float32), b.to(torch.float32)
-
-    def _pack_conv(self, conv, bn, ws=False, plus=None):
-        w, b = self._fold(conv, bn)
-        for other in ([plus] if isinstance(plus, tuple) else (plus or [])):      # conv(x_a) + conv'(x_b) = one conv over [x_a | x_b]
-            w2, b2 = self._fold(*other)
-            if w2.shape[0] != w.shape[0] or w2.shape[2:] != w.shape[2:]:
-                raise ValueError("%s + %s: different geometry" % (conv, other[0]))
-            w, b = torch.cat([w, w2], dim=1), b + b2
-        cout, cin, kh, kw = w.shape
-        cout_pad = _round_up(cout, 32)
-        wp = torch.zeros(kh * kw, cout_pad, cin, dtype=torch.float32)
-        wp[:, :cout] = w.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin)
-        self._wexp = 0
-        if ws:
-            from .f16x2 import pack_weights_ws
-            packed, self._wexp = pack_weights_ws(wp)           # scaled by 2^wexp: any finite magnitude fits
-            wbytes = packed.numpy().tobytes()
-        else:
-            wbytes = encode_weights(wp, self.dtype)
-        bp = torch.zeros(cout_pad, dtype=torch.float32)
-        bp[:cout] = b
-        return self._put(wbytes), self._put(bp.numpy().tobytes()), cout, cin, kh, cout_pad
-
-    # ------------------------------------------------------------------ emission
-    def _new(self, c, h, w):
-        t = _T(len(self._tensors), c, h, w)
-        self._tensors.append(t)
-        return t
-
-    def _conv(self, x, conv, bn, stride=1, relu=True, res=None, ups=(), to_output=False, group=0, in_coff=None,
-              into=None, plus=None, chain=None):
-        """One conv + folded BatchNorm (+ residual / upsampled addends, + ReLU).  ``in_coff``: read the ``cin`` channels
-        of ``x`` that start there (a channel-slice view); ``into = (tensor, coff)``: write the output into that slice of
-        an existing wider tensor; ``plus = (conv', bn')``: a second conv + BatchNorm of the same geometry whose input
-        channels FOLLOW this conv's in ``x`` and whose result is summed in -- one conv over the concatenated channels
-        with the weights side by side and the biases added; ``chain = (conv'', bn'')``: a 1x1 conv + BatchNorm + ReLU
-        applied to this conv's result in the same launch (udp_conv_op.chain_cout) -- returns ``(out, chained out)``."""
-        # (the output conv writes NCHW fp32 from the weight-stationary kernel too; UDP_POSE_HEAD_WS=0: the LDS-staged kernel)
-        head_ws = to_output and stride == 1 and os.environ.get("UDP_POSE_HEAD_WS", "1") != "0"
-        ws = self.use_ws and (not to_output or head_ws) and int(self.sd[conv + ".weight"].shape[2]) in (1, 3) and stride in (1, 2)
-        w_off, b_off, cout, cin, ks, cout_pad = self._pack_conv(conv, bn, ws, plus)
-        if isinstance(x, _V):                    # ``x`` / ``res`` may be channel-slice views (_V) of wider tensors
-            if cin != x.c:
-                raise ValueError("%s: weight expects %d input channels, view has %d" % (conv, cin, x.c))
-            x, in_coff = x.t, x.coff
-        res_view = res if isinstance(res, _V) else None
-        if res_view is not None:
-            res = res_view.t
-        if cin != x.c and in_coff is None:
-            raise ValueError("%s: weight expects %d input channels, tensor has %d" % (conv, cin, x.c))
-        pad = ks // 2
-        ho = (x.h + 2 * pad - ks) // stride + 1
-        wo = (x.w + 2 * pad - ks) // stride + 1
-        out = None if to_output else (into[0] if into else self._new(cout, ho, wo))
-        op = dict(kind=_lib.UDP_OP_CONV, ks=ks, stride=stride, relu=int(relu), cin=cin, cout=cout,
-                  cout_pad=cout_pad, hin=x.h, win=x.w, hout=ho, wout=wo, inp=x, out=out, res=res,
-                  ups=list(ups), w_off=w_off, b_off=b_off, name=conv, group=group, wfmt=int(ws), wexp=self._wexp)
-        if in_coff is not None:
-            if in_coff + cin > x.c:
-                raise ValueError("%s: channels %d..%d of a %d-channel tensor" % (conv, in_coff, in_coff + cin, x.c))
-            op.update(in_coff=in_coff, in_pitch=x.c)
-        if res_view is not None:
-            if res_view.c != cout or (res.h, res.w) != (ho, wo):
-                raise ValueError("%s: residual view does not match the output" % conv)
-            op.update(res_coff=res_view.coff, res_pitch=res.c, res_c=cout)
-        if into:
-            if (out.h, out.w) != (ho, wo) or into[1] + cout > out.c:
-                raise ValueError("%s: output slice does not fit its tensor" % conv)
-            op.update(out_coff=into[1], out_pitch=out.c)
-        if chain is not None:
-            from .f16x2 import pack_weights_ws
-            w2, b2 = self._fold(*chain)
-            c2 = int(w2.shape[0])
-            if not ws or ks != 1 or tuple(w2.shape[1:]) != (cout, 1, 1) or cout_pad != cout or c2 % 32:
-                raise ValueError("%s -> %s: not a chain of split-fp16 1x1 convs" % (conv, chain[0]))
-            packed, wexp2 = pack_weights_ws(w2.reshape(1, c2, cout))
-            z = self._new(c2, ho, wo)
-            op.update(chain_out=z, chain_cout=c2, chain_relu=1, chain_wexp=wexp2, w2_off=self._put(packed.numpy().tobytes()),
-                      b2_off=self._put(b2.numpy().tobytes()), chain_name=chain[0])
-        self._ops.append(op)
-        return (out, op["chain_out"]) if chain is not None else out
+        super().__init__(state_dict, in_h, in_w, dtype)
 
     def _next_group(self):
         self._groups += 1
@@ -234,12 +54,10 @@ class HRNetProgram:
                 and tuple(self.sd[q + ".conv2.weight"].shape) == (32, 32, 3, 3))
 
     def _block(self, x, q):
-        w1, b1, _, _, _, _ = self._pack_conv(q + ".conv1", q + ".bn1")
-        w2, b2, _, _, _, _ = self._pack_conv(q + ".conv2", q + ".bn2")
+        w1, b1 = self._pack(*self._fold(q + ".conv1", q + ".bn1"))[:2]
+        w2, b2 = self._pack(*self._fold(q + ".conv2", q + ".bn2"))[:2]
         out = self._new(32, x.h, x.w)
-        self._ops.append(dict(kind=_lib.UDP_OP_BLOCK, ks=3, stride=1, relu=1, cin=32, cout=32, cout_pad=32, hin=x.h,
-                              win=x.w, hout=x.h, wout=x.w, inp=x, out=out, res=None, ups=[], w_off=w1, b_off=b1,
-                              w2_off=w2, b2_off=b2, name=q + ".block"))
+        self._emit(_lib.UDP_OP_BLOCK, q + ".block", x, out, ks=3, relu=1, w_off=w1, b_off=b1, w2_off=w2, b2_off=b2)
         return out
 
     def _psa(self, x, p):
@@ -256,34 +74,22 @@ class HRNetProgram:
             raise ValueError("%s: PSA parameter shapes do not match planes=%d" % (p, C))
         w_off = self._put(block.numpy().tobytes())
         f = 4 // storage_bytes(self.dtype)                               # fp32 side rows, counted in dtype elements
-        base = dict(ks=1, stride=1, relu=0, cout_pad=_round_up(C, 32), hin=x.h, win=x.w, hout=x.h, wout=x.w,
-                    res=None, ups=[], w_off=w_off, b_off=0)
+        geom = dict(cin=C, cout=C, hin=x.h, win=x.w, hout=x.h, wout=x.w, w_off=w_off)       # of the attended map, whatever the operand
         pooled = self._new(2 * C * f, 1, 1)
-        self._ops.append(dict(base, kind=_lib.UDP_OP_PSA_POOL, cin=C, cout=C, inp=x, out=pooled, name=p + ".pool"))
+        self._emit(_lib.UDP_OP_PSA_POOL, p + ".pool", x, pooled, **geom)
         mask = self._new((C + C // 2) * f, 1, 1)
-        self._ops.append(dict(base, kind=_lib.UDP_OP_PSA_MLP, cin=C, cout=C, inp=pooled, out=mask, name=p + ".mlp"))
+        self._emit(_lib.UDP_OP_PSA_MLP, p + ".mlp", pooled, mask, **geom)
         x1 = self._new(C, x.h, x.w)
-        self._ops.append(dict(base, kind=_lib.UDP_OP_PSA_SCALE, cin=C, cout=C, inp=x, res=mask, out=x1,
-                              name=p + ".scale"))
+        self._emit(_lib.UDP_OP_PSA_SCALE, p + ".scale", x, x1, res=mask, **geom)
         theta = self._conv(x1, p + ".conv_v_left", None, relu=False)
         x2 = self._new(C, x.h, x.w)
-        self._ops.append(dict(base, kind=_lib.UDP_OP_PSA_SP, cin=C // 2, cout=C, inp=theta, res=x1, ups=[(mask, 0)],
-                              out=x2, name=p + ".sp"))
+        self._emit(_lib.UDP_OP_PSA_SP, p + ".sp", theta, x2, res=x1, ups=[(mask, 0)], **dict(geom, cin=C // 2))
         return x2
 
     def _build(self):
         sd = self.sd
         H, W = self.in_h, self.in_w
-        # stem conv1 (VALU kernel on the NCHW fp32 input): weights fp32 [ky][kx][ci][cout]
-        w, b = self._fold("conv1", "bn1")
-        if tuple(w.shape) != (64, 3, 3, 3):
-            raise ValueError("conv1.weight must be [64,3,3,3]")
-        w_off = self._put(w.permute(2, 3, 1, 0).contiguous().numpy().tobytes())
-        b_off = self._put(b.numpy().tobytes())
-        x = self._new(64, H // 2, W // 2)
-        self._ops.append(dict(kind=_lib.UDP_OP_STEM, ks=3, stride=2, relu=1, cin=3, cout=64, cout_pad=64, hin=H,
-                              win=W, hout=H // 2, wout=W // 2, inp=None, out=x, res=None, ups=[], w_off=w_off,
-                              b_off=b_off, name="conv1"))
+        x = self._stem(_lib.UDP_OP_STEM, "conv1", "bn1", 3)
         # The first Bottleneck's projection shortcut (pose_hrnet.py:87-98: out = relu(bn3(conv3(t)) + bn_d(conv_d(x))))
         # is a second 1x1 conv of the same shape as conv3: with t and x side by side in one tensor the two are ONE
         # 1x1 conv over the concatenated channels -- the 4*planes-channel shortcut map is never written nor read back.
@@ -415,10 +221,7 @@ class HRNetProgram:
                     outs.append(self._conv(xs[0], "%s.fuse_layers.0.0.0" % p, None, ups=ups))
                 else:
                     out = self._new(xs[0].c, xs[0].h, xs[0].w)
-                    self._ops.append(dict(kind=_lib.UDP_OP_FUSE, ks=1, stride=1, relu=1, cin=xs[0].c, cout=xs[0].c,
-                                          cout_pad=_round_up(xs[0].c, 32), hin=xs[0].h, win=xs[0].w, hout=xs[0].h,
-                                          wout=xs[0].w, inp=xs[0], out=out, res=None, ups=ups, w_off=0, b_off=0,
-                                          name=p + ".fuse0"))
+                    self._emit(_lib.UDP_OP_FUSE, p + ".fuse0", xs[0], out, relu=1, ups=ups)
                     outs.append(out)
                 continue
             if i in cat:
@@ -446,141 +249,3 @@ class HRNetProgram:
                         res, ups = t, []
             outs.append(t)
         return outs
-
-    # ------------------------------------------------------------------ lanes + buffers
-    def _assign_buffers(self):
-        """Linear-scan buffer assignment plus the cross-lane dependency lists.
-
-        Lane = resolution level of the op's output (HRNet branch): ops of different lanes may run
-        concurrently, ordered only by (a) producer -> consumer edges and (b) buffer reuse: the new
-        writer of a physical buffer waits for the previous tenant's writer and readers.  Same-lane
-        predecessors are ordered by the stream itself and are not listed."""
-        h4 = self.in_h // 4
-        for op in self._ops:
-            lvl = 0
-            while (h4 >> lvl) > op["hout"] and lvl < _lib.MAX_LANES - 1:
-                lvl += 1
-            op["lane"] = lvl
-        self._ops[0]["lane"] = 0
-        producer = {}
-        readers = {}
-
-        def reads_of(op):        # every tensor the op reads (add2: addends of its second outputs, udp_conv_op.n_out2)
-            return [t for t in [op["inp"], op["res"]] + [u for u, _ in op["ups"]] + [a for a, _ in op.get("add2", [])]
-                    if t is not None]
-
-        for idx, op in enumerate(self._ops):
-            if op["out"] is not None:
-                if op["out"].id in producer:
-                    readers.setdefault(op["out"].id, []).append(producer[op["out"].id])   # earlier slice writers
-                producer[op["out"].id] = idx
-            for t in [t for t, _ in op.get("out2", [])] + ([op["chain_out"]] if op.get("chain_out") is not None else []):
-                producer[t.id] = idx
-            for t in reads_of(op):
-                readers.setdefault(t.id, []).append(idx)
-        last_use = {tid: max(r) for tid, r in readers.items()}
-        free = {}             # elems -> [(buffer id, previous tenant tensor id)]
-        self.buf_elems = []
-        phys = {}
-        pending = []
-        for idx, op in enumerate(self._ops):
-            deps = set()
-            for t in reads_of(op):
-                if t.id in producer:
-                    deps.add(producer[t.id])
-            out = op["out"]
-            if out is not None and out.id in phys:
-                deps.add(producer[out.id])      # later slice of a concat buffer: ordered after its other writers
-                out = None
-            for out in (([out] if out is not None else []) + [t for t, _ in op.get("out2", [])]
-                        + ([op["chain_out"]] if op.get("chain_out") is not None else [])):
-                pool = free.get(out.elems, [])
-                pick = None
-                for k in range(len(pool) - 1, -1, -1):
-                    b, old = pool[k]
-                    hazard = {producer[old]} | set(readers.get(old, []))
-                    cross = {d for d in (deps | hazard) if self._ops[d]["lane"] != op["lane"]}
-                    if len(cross) <= _lib.MAX_WAIT:
-                        pick = k
-                        deps |= hazard
-                        break
-                if pick is not None:
-                    phys[out.id] = pool.pop(pick)[0]
-                else:
-                    phys[out.id] = len(self.buf_elems)
-                    self.buf_elems.append(out.elems)
-            cross = sorted(d for d in deps if self._ops[d]["lane"] != op["lane"])
-            if len(cross) > _lib.MAX_WAIT:
-                raise RuntimeError("op %s has %d cross-lane dependencies (max %d)" % (op["name"], len(cross), _lib.MAX_WAIT))
-            op["wait"] = cross
-            # members of a launch group run concurrently: a buffer one of them reads for the last time
-            # must not be handed to a later member of the same group
-            g = op.get("group", 0)
-            nxt = self._ops[idx + 1].get("group", 0) if idx + 1 < len(self._ops) else 0
-            for t in reads_of(op):
-                if last_use.get(t.id) == idx and t.id in phys:
-                    pending.append((t.elems, phys[t.id], t.id))
-                    last_use[t.id] = -1
-            if g == 0 or nxt != g:
-                for elems, b, tid in pending:
-                    free.setdefault(elems, []).append((b, tid))
-                pending = []
-        self._phys = phys
-
-    # ------------------------------------------------------------------ output
-    def ops_array(self):
-        arr = (_lib.ConvOp * len(self._ops))()
-        for i, op in enumerate(self._ops):
-            o = arr[i]
-            for f in ("kind", "ks", "stride", "relu", "cin", "cout", "cout_pad", "hin", "win", "hout", "wout",
-                      "w_off", "b_off"):
-                setattr(o, f, op[f])
-            o.in_buf = _lib.UDP_BUF_NONE if op["inp"] is None else self._phys[op["inp"].id]
-            o.out_buf = (_lib.UDP_BUF_NONE if op.get("no_out") else _lib.UDP_BUF_OUTPUT) if op["out"] is None else self._phys[op["out"].id]
-            o.res_buf = _lib.UDP_BUF_NONE if op["res"] is None else self._phys[op["res"].id]
-            for f in ("in_coff", "in_pitch", "out_coff", "out_pitch", "res_coff", "res_pitch", "w2_off", "b2_off", "group", "wfmt", "wexp"):
-                setattr(o, f, op.get(f, 0))
-            if op.get("chain_out") is not None:
-                o.chain_cout, o.chain_relu, o.chain_wexp = op["chain_cout"], op["chain_relu"], op["chain_wexp"]
-                o.chain_buf = self._phys[op["chain_out"].id]
-            o.n_out2 = len(op.get("out2", []))
-            for k, ((t2, c2), (ta, ca)) in enumerate(zip(op.get("out2", []), op.get("add2", []))):
-                o.out2_buf[k], o.out2_coff[k], o.out2_pitch[k] = self._phys[t2.id], c2, t2.c
-                o.add2_buf[k], o.add2_coff[k], o.add2_pitch[k] = self._phys[ta.id], ca, ta.c
-            o.lane = op["lane"]
-            o.n_wait = len(op["wait"])
-            for k, d in enumerate(op["wait"]):
-                o.wait_op[k] = d
-            o.n_up = len(op["ups"])
-            for u, (t, s) in enumerate(op["ups"]):
-                o.up_buf[u] = self._phys[t.id]
-                o.up_shift[u] = s
-        return arr
-
-    def weight_blob(self):
-        blob = np.zeros(_round_up(self._blob_size, 256), dtype=np.uint8)
-        for off, b in self._blob:
-            blob[off:off + len(b)] = np.frombuffer(b, dtype=np.uint8)
-        return blob
-
-    def describe(self):
-        return [(op["name"], op["kind"], op["ks"], op["stride"], op["cin"], op["cout"], op["hout"], op["wout"])
-                for op in self._ops]
-
-    def macs_per_image(self):
-        return sum(op["ks"] ** 2 * op["cin"] * op["cout"] * op["hout"] * op["wout"] * (2 if op["kind"] == _lib.UDP_OP_BLOCK else 1)
-                   + op.get("chain_cout", 0) * op["cout"] * op["hout"] * op["wout"]
-                   for op in self._ops
-                   if op["kind"] in (_lib.UDP_OP_STEM, _lib.UDP_OP_CONV, _lib.UDP_OP_STEM7, _lib.UDP_OP_BLOCK))
-
-    def activation_elems_per_image(self):
-        """Layer-wise algorithmic traffic: every op reads its inputs once and writes its output once."""
-        n = 0
-        for op in self._ops:
-            n += op["hin"] * op["win"] * op["cin"] + op["hout"] * op["wout"] * op["cout"]
-            if op["res"] is not None:
-                n += op["res"].elems // op["res"].c * op.get("res_c", op["res"].c)
-            n += sum(t.elems for t, _ in op["ups"])
-            if op.get("chain_out") is not None:
-                n += op["chain_out"].elems
-        return n

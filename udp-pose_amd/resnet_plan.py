@@ -6,10 +6,10 @@ NUM_DECONV_LAYERS x [ConvTranspose2d(k=4, s=2, p=1) + BN + ReLU] (:155-193) and 
 bias (:128-136) writing the NCHW fp32 heat-maps.  ``conv3 + bn3 + shortcut + ReLU`` of a Bottleneck is one conv with
 the residual in its epilogue; every deconv layer is one UDP_OP_DECONV launch (csrc/deconv.hip).
 """
-from . import _lib
-from .hrnet_plan import BN_EPS, HRNetProgram, _round_up, encode_weights
-
 import torch
+
+from . import _lib
+from .program import Program, _round_up, encode_weights
 
 # resnet_spec of pose_resnet.py:254-260 (Bottleneck depths only; BasicBlock 18 / 34 ship in no YAML)
 RESNET_LAYERS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -62,41 +62,26 @@ class _Tracked(dict):
         return super().get(k, default)
 
 
-class PoseResNetProgram(HRNetProgram):
+class PoseResNetProgram(Program):
     def __init__(self, state_dict, spec, in_h, in_w, dtype="f32"):
         if dtype not in ("f32", "f16x2"):
             raise ValueError("pose_resnet: dtype %r; supported storage modes are 'f32' and 'f16x2' (the deconv kernel "
                              "has no bf16 form)" % (dtype,))
         self.spec = spec
-        super().__init__(state_dict, {}, in_h, in_w, dtype)
+        super().__init__(state_dict, in_h, in_w, dtype)
 
     @property
     def consumed_keys(self):
         return set(self.sd.used)
 
-    def _op(self, kind, x, out, name, **kw):
-        op = dict(kind=kind, ks=kw.pop("ks", 1), stride=kw.pop("stride", 1), relu=int(kw.pop("relu", 0)), cin=x.c,
-                  cout=out.c, cout_pad=_round_up(out.c, 32), hin=x.h, win=x.w, hout=out.h, wout=out.w, inp=x, out=out,
-                  res=None, ups=[], w_off=0, b_off=0, name=name)
-        op.update(kw)
-        self._ops.append(op)
-
     def _deconv(self, x, d):
         """deconv_layers[3d] (ConvTranspose2d, [cin, cout, 4, 4], bias if DECONV_WITH_BIAS) + [3d+1] (BatchNorm) + ReLU:
         the BatchNorm scale folds along dim 1 (the output channels), the deconv bias into the BatchNorm bias."""
-        sd = self.sd
-        q, bn = "deconv_layers.%d" % (3 * d), "deconv_layers.%d" % (3 * d + 1)
-        w = sd[q + ".weight"].detach().to(torch.float64).cpu()
+        q = "deconv_layers.%d" % (3 * d)
+        w, b = self._fold(q, "deconv_layers.%d" % (3 * d + 1), axis=1)
         cin, cout = int(w.shape[0]), int(w.shape[1])
         if cin != x.c:
             raise ValueError("%s expects %d input channels, got %d" % (q, cin, x.c))
-        bias = sd.get(q + ".bias")
-        b = bias.detach().to(torch.float64).cpu() if bias is not None else torch.zeros(cout, dtype=torch.float64)
-        s = sd[bn + ".weight"].detach().to(torch.float64).cpu() / torch.sqrt(
-            sd[bn + ".running_var"].detach().to(torch.float64).cpu() + BN_EPS)
-        w = (w * s[None, :, None, None]).to(torch.float32)
-        b = ((b - sd[bn + ".running_mean"].detach().to(torch.float64).cpu()) * s
-             + sd[bn + ".bias"].detach().to(torch.float64).cpu()).to(torch.float32)
         cout_pad = _round_up(cout, 32)
         from .f16x2 import deconv_phase_taps, pack_deconv_weights_ws
         wexp = 0
@@ -108,25 +93,17 @@ class PoseResNetProgram(HRNetProgram):
         bp = torch.zeros(cout_pad, dtype=torch.float32)
         bp[:cout] = b
         out = self._new(cout, 2 * x.h, 2 * x.w)
-        self._op(_lib.UDP_OP_DECONV, x, out, q, ks=4, stride=2, relu=1, cout_pad=cout_pad, w_off=w_off,
-                 b_off=self._put(bp.numpy().tobytes()), wfmt=int(self.dtype == "f16x2"), wexp=wexp)
+        self._emit(_lib.UDP_OP_DECONV, q, x, out, ks=4, stride=2, relu=1, w_off=w_off,
+                   b_off=self._put(bp.numpy().tobytes()), wfmt=int(self.dtype == "f16x2"), wexp=wexp)
         return out
 
     def _build(self):
         self.sd = _Tracked(self.sd)
         sd = self.sd
         H, W = self.in_h, self.in_w
-        w, b = self._fold("conv1", "bn1")
-        if tuple(w.shape) != (64, 3, 7, 7):
-            raise ValueError("conv1.weight must be [64,3,7,7]")
-        w_off = self._put(w.permute(2, 3, 1, 0).contiguous().numpy().tobytes())     # [ky][kx][ci][cout]
-        b_off = self._put(b.numpy().tobytes())
-        x = self._new(64, H // 2, W // 2)
-        self._ops.append(dict(kind=_lib.UDP_OP_STEM7, ks=7, stride=2, relu=1, cin=3, cout=64, cout_pad=64, hin=H, win=W,
-                              hout=H // 2, wout=W // 2, inp=None, out=x, res=None, ups=[], w_off=w_off, b_off=b_off,
-                              name="conv1"))
+        x = self._stem(_lib.UDP_OP_STEM7, "conv1", "bn1", 7)
         pooled = self._new(64, H // 4, W // 4)
-        self._op(_lib.UDP_OP_MAXPOOL, x, pooled, "maxpool", ks=3, stride=2)
+        self._emit(_lib.UDP_OP_MAXPOOL, "maxpool", x, pooled, ks=3, stride=2)
         x = pooled
         for li, nblk in enumerate(self.spec["layers"], start=1):          # _make_layer (:138-153)
             for k in range(nblk):
@@ -147,7 +124,3 @@ class PoseResNetProgram(HRNetProgram):
         for k in sd:
             if k.endswith("num_batches_tracked"):
                 sd.used.add(k)                                              # BatchNorm bookkeeping, not an operand
-
-    def macs_per_image(self):
-        deconv = sum(4 * op["cin"] * op["cout"] * op["hout"] * op["wout"] for op in self._ops if op["kind"] == _lib.UDP_OP_DECONV)
-        return super().macs_per_image() + deconv

@@ -12,72 +12,25 @@ closing 1x1 conv's weight columns are scattered to the padded positions with zer
 3x3 convs read / write channel slices in place, and the pad channels stay exactly 0 (zero weights,
 zero bias, ReLU).  The ``a + b`` that precedes most 3x3 convs is one element-wise launch.
 """
-import torch
-
 import os
 
 from . import _lib
-from .hrnet_plan import HRNetProgram, _round_up, encode_weights
+from .program import Program, _round_up
 
 
-class RSNProgram(HRNetProgram):
+class RSNProgram(Program):
     def __init__(self, state_dict, in_h, in_w, dtype="f32", chl_num=256):
         self.chl_num = chl_num
-        super().__init__(state_dict, {}, in_h, in_w, dtype)
+        super().__init__(state_dict, in_h, in_w, dtype)
 
-    # ---- weights -------------------------------------------------------------------------------
     def _fold_cbr(self, name):
-        """conv (with bias) + BatchNorm(eval) folded in fp64 -> fp32 weight [cout,cin,k,k], bias [cout]."""
-        sd = self.sd
-        w = sd[name + ".conv.weight"].detach().to(torch.float64).cpu()
-        b = sd[name + ".conv.bias"].detach().to(torch.float64).cpu()
-        g = sd[name + ".bn.weight"].detach().to(torch.float64).cpu()
-        beta = sd[name + ".bn.bias"].detach().to(torch.float64).cpu()
-        mean = sd[name + ".bn.running_mean"].detach().to(torch.float64).cpu()
-        var = sd[name + ".bn.running_var"].detach().to(torch.float64).cpu()
-        s = g / torch.sqrt(var + 1e-5)
-        return (w * s[:, None, None, None]).to(torch.float32), ((b - mean) * s + beta).to(torch.float32)
+        """conv_bn_relu module ``name`` (conv with bias + BatchNorm) -> folded fp32 weight [cout,cin,k,k], bias [cout]."""
+        return self._fold(name + ".conv", name + ".bn")
 
-    def _pack(self, w, b, out_map=None, in_map=None, cout_t=None, cin_t=None, ws=False):
-        """Pack to [k*k][cout_pad][cin_t]; out_map / in_map scatter real channels to padded positions.  ``ws``: the
-        fragment-major split-fp16 layout of the weight-stationary kernels (udp_conv_op.wfmt = 1), as HRNetProgram packs
-        its convs."""
-        cout, cin, kh, kw = w.shape
-        cout_t = cout_t or cout
-        cin_t = cin_t or cin
-        out_map = out_map if out_map is not None else list(range(cout))
-        in_map = in_map if in_map is not None else list(range(cin))
-        cout_pad = _round_up(cout_t, 32)
-        wp = torch.zeros(kh * kw, cout_pad, cin_t, dtype=torch.float32)
-        oi = torch.tensor(out_map)
-        ii = torch.tensor(in_map)
-        wp[:, oi[:, None], ii[None, :]] = w.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin)
-        bp = torch.zeros(cout_pad, dtype=torch.float32)
-        bp[oi] = b
-        self._wexp = 0
-        if ws:
-            from .f16x2 import pack_weights_ws
-            packed, self._wexp = pack_weights_ws(wp)
-            wbytes = packed.numpy().tobytes()
-        else:
-            wbytes = encode_weights(wp, self.dtype)
-        return self._put(wbytes), self._put(bp.numpy().tobytes()), cout_t, cin_t, kh, cout_pad
-
-    # ---- emission ------------------------------------------------------------------------------
-    def _op(self, kind, x, out, name, ks=1, stride=1, relu=0, cin=None, cout=None, cout_pad=None, res=None,
-            w_off=0, b_off=0, in_coff=0, out_coff=0, res_coff=0, hout=None, wout=None, wfmt=0, wexp=0,
-            out2=(), add2=(), no_out=False):
-        cin = cin if cin is not None else x.c
-        cout = cout if cout is not None else out.c
-        self._ops.append(dict(kind=kind, ks=ks, stride=stride, relu=int(relu), cin=cin, cout=cout,
-                              cout_pad=cout_pad or _round_up(cout, 32), hin=x.h if x is not None else self.in_h,
-                              win=x.w if x is not None else self.in_w, hout=hout or (out.h if out is not None else 0),
-                              wout=wout or (out.w if out is not None else 0), inp=x, out=out, res=res, ups=[],
-                              w_off=w_off, b_off=b_off, name=name, in_coff=in_coff,
-                              in_pitch=x.c if x is not None else 0, out_coff=out_coff,
-                              out_pitch=out.c if out is not None else 0, res_coff=res_coff,
-                              res_pitch=res.c if res is not None else 0, wfmt=wfmt, wexp=wexp,
-                              out2=list(out2), add2=list(add2), no_out=no_out))
+    def _op(self, kind, x, out, name, res=None, **fields):
+        """An op over channel-slice views: every operand carries its tensor's channel count as pitch."""
+        self._emit(kind, name, x, out, res=res, in_pitch=x.c, out_pitch=out.c if out is not None else 0,
+                   res_pitch=res.c if res is not None else 0, **fields)
 
     def _conv_v(self, x, name, out=None, ks=None, stride=1, relu=True, res=None, in_coff=0, cin_view=None,
                 out_coff=0, out_map=None, in_map=None, cout_t=None, cin_t=None, to_output=False, sums=(), keep=True):
@@ -90,7 +43,7 @@ class RSNProgram(HRNetProgram):
         head_ws = to_output and stride == 1 and os.environ.get("UDP_POSE_HEAD_WS", "1") != "0"
         ws = (self.use_ws and (not to_output or head_ws) and int(w.shape[2]) in (1, 3) and stride in (1, 2)
               and os.environ.get("UDP_POSE_RSN_WS", "1") != "0")
-        w_off, b_off, cout, cin, k, cout_pad = self._pack(w, b, out_map, in_map, cout_t, cin_t, ws=ws)
+        w_off, b_off, cout, cin, k, cout_pad, wexp = self._pack(w, b, ws, out_map, in_map, cout_t, cin_t)
         if cin_view is not None and cin_view != cin:
             raise ValueError("%s: view has %d channels, weights expect %d" % (name, cin_view, cin))
         pad = k // 2
@@ -103,7 +56,7 @@ class RSNProgram(HRNetProgram):
         s2 = [self._new(cout, ho, wo) for _ in sums]
         self._op(_lib.UDP_OP_CONV, x, out, name, ks=k, stride=stride, relu=relu, cin=cin, cout=cout, cout_pad=cout_pad,
                  res=res, w_off=w_off, b_off=b_off, in_coff=in_coff, out_coff=out_coff, hout=ho, wout=wo,
-                 wfmt=int(ws), wexp=self._wexp, out2=[(t, 0) for t in s2], add2=list(sums), no_out=not keep)
+                 wfmt=int(ws), wexp=wexp, out2=[(t, 0) for t in s2], add2=list(sums), no_out=not keep)
         return (out, s2) if sums else out
 
     def _add(self, a, a_coff, b, b_coff, c, name):
@@ -142,21 +95,17 @@ class RSNProgram(HRNetProgram):
             _, (t43,) = c3(t42, 0, "2_4_2", sums=[(cat, 2 * bp)], keep=False)            # out_4_2 + cat[2]
             o43 = c3(t43, 0, "2_4_3")
             c3(o43, 0, "2_4_4", out=cat, out_coff=3 * bp)                                # out_4_4 -> cat[3]
-            r = x
-            if (p + ".downsample.conv.weight") in sd:
-                r = self._conv_v(x, p + ".downsample", stride=stride, relu=False)
-            return self._conv_v(cat, p + ".conv_bn_relu3", res=r, in_map=scatter, cin_t=4 * bp)
-
-        c3(s, 0, "2_1_1", out=cat, out_coff=0)                                   # out_1_1 -> cat[0]
-        o21 = c3(self._add(s, bp, cat, 0, bp, p + ".add21"), 0, "2_2_1")
-        c3(o21, 0, "2_2_2", out=cat, out_coff=bp)                                # out_2_2 -> cat[1]
-        o31 = c3(self._add(s, 2 * bp, o21, 0, bp, p + ".add31"), 0, "2_3_1")
-        o32 = c3(self._add(o31, 0, cat, bp, bp, p + ".add32"), 0, "2_3_2")
-        c3(o32, 0, "2_3_3", out=cat, out_coff=2 * bp)                            # out_3_3 -> cat[2]
-        o41 = c3(self._add(s, 3 * bp, o31, 0, bp, p + ".add41"), 0, "2_4_1")
-        o42 = c3(self._add(o41, 0, o32, 0, bp, p + ".add42"), 0, "2_4_2")
-        o43 = c3(self._add(o42, 0, cat, 2 * bp, bp, p + ".add43"), 0, "2_4_3")
-        c3(o43, 0, "2_4_4", out=cat, out_coff=3 * bp)                            # out_4_4 -> cat[3]
+        else:
+            c3(s, 0, "2_1_1", out=cat, out_coff=0)                                   # out_1_1 -> cat[0]
+            o21 = c3(self._add(s, bp, cat, 0, bp, p + ".add21"), 0, "2_2_1")
+            c3(o21, 0, "2_2_2", out=cat, out_coff=bp)                                # out_2_2 -> cat[1]
+            o31 = c3(self._add(s, 2 * bp, o21, 0, bp, p + ".add31"), 0, "2_3_1")
+            o32 = c3(self._add(o31, 0, cat, bp, bp, p + ".add32"), 0, "2_3_2")
+            c3(o32, 0, "2_3_3", out=cat, out_coff=2 * bp)                            # out_3_3 -> cat[2]
+            o41 = c3(self._add(s, 3 * bp, o31, 0, bp, p + ".add41"), 0, "2_4_1")
+            o42 = c3(self._add(o41, 0, o32, 0, bp, p + ".add42"), 0, "2_4_2")
+            o43 = c3(self._add(o42, 0, cat, 2 * bp, bp, p + ".add43"), 0, "2_4_3")
+            c3(o43, 0, "2_4_4", out=cat, out_coff=3 * bp)                            # out_4_4 -> cat[3]
         r = x
         if (p + ".downsample.conv.weight") in sd:
             r = self._conv_v(x, p + ".downsample", stride=stride, relu=False)
@@ -164,15 +113,7 @@ class RSNProgram(HRNetProgram):
 
     def _build(self):
         H, W = self.in_h, self.in_w
-        w, b = self._fold_cbr("top.conv")
-        if tuple(w.shape) != (64, 3, 7, 7):
-            raise ValueError("top.conv.conv.weight must be [64,3,7,7]")
-        w_off = self._put(w.permute(2, 3, 1, 0).contiguous().numpy().tobytes())     # [ky][kx][ci][cout]
-        b_off = self._put(b.numpy().tobytes())
-        x = self._new(64, H // 2, W // 2)
-        self._ops.append(dict(kind=_lib.UDP_OP_STEM7, ks=7, stride=2, relu=1, cin=3, cout=64, cout_pad=64, hin=H, win=W,
-                              hout=H // 2, wout=W // 2, inp=None, out=x, res=None, ups=[], w_off=w_off, b_off=b_off,
-                              name="top.conv"))
+        x = self._stem(_lib.UDP_OP_STEM7, "top.conv.conv", "top.conv.bn", 7, name="top.conv")
         pooled = self._new(64, H // 4, W // 4)
         self._op(_lib.UDP_OP_MAXPOOL, x, pooled, "top.maxpool", ks=3, stride=2)
         x = pooled
