@@ -464,6 +464,63 @@ int udp_adam_coefficients(float lr, float beta1, float beta2, int step, float* c
 int udp_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t count, float beta1, float beta2,
                       float eps, const float* coef_dev, float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Training of the polarized self-attention block of pose_hrnet_psa.  Replaces
+ * PSA_s.forward (deep_hrnet/lib/models/PSA.py:190-269: spatial_pool :190-222,
+ * channel_pool :224-258) under model.train() and its autograd backward.
+ *
+ * New symbols rather than new udp_conv_op kinds: the backward reads and writes more tensors (gradient maps, ten
+ * parameter gradients, a save area) than udp_conv2d_fused has arguments for.  They are an addition old callers never
+ * see, so UDP_POSE_ABI_VERSION stays as it is.
+ *
+ * One block, per image on an NHWC map x [h*w][c] of `dtype` (UDP_F32 | UDP_BF16; c divides 256, a multiple of 16,
+ * at least 32):
+ *   a = softmax_HW(wq.x_p)   xbar = sum_p a_p x_p   m = sigmoid(W2 relu(LN(W1 Wv xbar + b1)) + b2)   x1 = x * m[c]
+ *   gbar = Wg mean_p(x1)     theta = Wt x1          s_p = sigmoid(sum_j gbar_j softmax_HW(theta_j)_p) x2 = x1 * s_p
+ * theta (c/2 channels) and its backward (dWt, dx1 += Wt^T dtheta) are the caller's 1x1 conv: udp_conv2d_fused,
+ * udp_conv2d_wgrad.  Call order of a step:
+ *   udp_psa_train_fwd_pool   reads x, w               writes x1
+ *   (theta = conv1x1(x1, conv_v_left))
+ *   udp_psa_train_fwd_sp     reads x1, theta          writes x2
+ *   ...
+ *   udp_psa_train_bwd_sp     reads dx2, x1, theta, w  writes dtheta, dx1 (= dx2 * s_p + Wg^T dgbar / HW)
+ *   (dx1 += conv1x1(dtheta, conv_v_left^T); d conv_v_left = wgrad(x1, dtheta))
+ *   udp_psa_train_bwd_pool   reads dx1, x, w          writes dx
+ *   udp_psa_train_bwd_params                          writes dw (overwritten, not accumulated; may run on another
+ *                                                     stream ordered behind udp_psa_train_bwd_pool)
+ * `save` (udp_psa_train_save_floats(n, h, w, c) floats, 0 for an unsupported shape) carries what the forward keeps
+ * for the backward (soft-max logits and statistics, LayerNorm statistics, r, m, gbar, s_p) and the per-image partial
+ * sums; it belongs to one block from its fwd_pool to its bwd_params.  All reductions are fp32 in a fixed order
+ * (partial rows per pixel chunk added in row order, images in image order): no atomics, bit-identical reruns.
+ * w / dw: fp32, the reference's tensors flattened, in registration order without conv_v_left --
+ *   0 conv_q_right.weight [c]       1 conv_v_right.weight [c/2][c]  2 conv_up.0.weight [c/8][c/2]  3 conv_up.0.bias [c/8]
+ *   4 conv_up.1.weight (LN) [c/8]   5 conv_up.1.bias (LN) [c/8]     6 conv_up.3.weight [c][c/8]    7 conv_up.3.bias [c]
+ *   8 conv_q_left.weight [c/2][c]   -- each 16-byte aligned.
+ * Every call checks the pointers it uses (UDP_ERR_ARG), the shape and dtype (UDP_ERR_UNSUPPORTED for a channel count
+ * outside the range above and for UDP_F16X2) and the size of `save` (UDP_ERR_WORKSPACE) before it launches anything.
+ * ------------------------------------------------------------------------- */
+typedef struct udp_psa_train_args {
+  const float* w[9];
+  float* dw[9];
+  const void* x;       /* [n][h*w][c]   block input */
+  void* x1;            /* [n][h*w][c]   x * m            (written by fwd_pool, read by fwd_sp / bwd_sp) */
+  const void* theta;   /* [n][h*w][c/2] conv_v_left(x1) */
+  void* x2;            /* [n][h*w][c]   block output */
+  const void* dx2;     /* gradient of x2 */
+  void* dtheta;        /* gradient of theta */
+  void* dx1;           /* gradient of x1: written by bwd_sp, completed by the caller's conv, read by bwd_pool */
+  void* dx;            /* gradient of x */
+  float* save;
+  size_t save_floats;
+  int32_t n, h, w_px, c;   /* images, map height, map width, channels */
+} udp_psa_train_args;
+size_t udp_psa_train_save_floats(int n, int h, int w, int c);
+int udp_psa_train_fwd_pool(const udp_psa_train_args* args, int dtype, void* stream);
+int udp_psa_train_fwd_sp(const udp_psa_train_args* args, int dtype, void* stream);
+int udp_psa_train_bwd_sp(const udp_psa_train_args* args, int dtype, void* stream);
+int udp_psa_train_bwd_pool(const udp_psa_train_args* args, int dtype, void* stream);
+int udp_psa_train_bwd_params(const udp_psa_train_args* args, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

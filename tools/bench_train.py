@@ -15,6 +15,8 @@ ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--dtype", default="f32")
 ap.add_argument("--target", default="gaussian")
 ap.add_argument("--backend", default="nccl")
+ap.add_argument("--model", default="pose_hrnet", choices=("pose_hrnet", "pose_hrnet_psa"),
+                help="pose_hrnet_psa: a polarized self-attention block in every BasicBlock (the reference's PSA YAMLs)")
 ap.add_argument("--no-graph", action="store_true", help="one ctypes launch per kernel instead of replaying the captured step")
 a = ap.parse_args()
 # one process per GPU under torch.distributed.run (backend nccl = RCCL); plain `python` = one GPU
@@ -25,8 +27,9 @@ if world > 1:
     # --backend gloo: several ranks on ONE GPU (the one-GPU test box); RCCL needs a device per rank
     dist.init_process_group(a.backend, rank=rank, world_size=world)
 nj = 17
-sd = synth.synth_state_dict(synth.W32_EXTRA, nj, a.target, seed=0)
-tr = HRNetTrainer({"MODEL": {"EXTRA": synth.W32_EXTRA, "NUM_JOINTS": nj, "TARGET_TYPE": a.target}}, sd, dtype=a.dtype)
+psa = a.model == "pose_hrnet_psa"
+sd = synth.synth_state_dict(synth.W32_EXTRA, nj, a.target, seed=0, psa=psa)
+tr = HRNetTrainer({"MODEL": {"EXTRA": synth.W32_EXTRA, "NUM_JOINTS": nj, "TARGET_TYPE": a.target}}, sd, dtype=a.dtype, psa=psa)
 x = torch.from_numpy(synth.synth_crops(a.batch, 256, 192, seed=1 + rank)).cuda()
 c = nj * (3 if a.target == "offset" else 1)
 tg = torch.from_numpy(synth.synth_heatmaps(a.batch, nj, 64, 48, seed=2, channels_per_joint=c // nj)).cuda()
@@ -61,11 +64,12 @@ if world > 1:
 if rank == 0:
     import json
     from udp_pose_amd.hrnet_plan import HRNetProgram
-    macs = HRNetProgram(sd, synth.W32_EXTRA, 256, 192, "f32").macs_per_image()
+    plain = {k: v for k, v in sd.items() if ".deattn." not in k}          # conv FLOPs of the backbone (theta's 1x1 convs not counted)
+    macs = HRNetProgram(plain, synth.W32_EXTRA, 256, 192, "f32").macs_per_image()
     flops = 3 * 2.0 * macs * a.batch                     # forward + input gradient + weight gradient
     peak = {"f32": 157.3, "bf16": 2500.0}[a.dtype]
     tf = flops / (dev * 1e-3) / 1e12
-    print(json.dumps({"metric": "images/sec HRNet-W32 256x192 training step (fwd + JointsMSELoss + bwd + Adam"
+    print(json.dumps({"model": a.model, "metric": "images/sec HRNet-W32 256x192 training step (fwd + JointsMSELoss + bwd + Adam"
                                 + (" + gradient all-reduce)" if world > 1 else ")"),
                       "value": round(a.batch * world / wall * 1e3, 1), "unit": "images/s", "n_gpus": world,
                       "ms_per_step": round(wall, 3), "dtype": a.dtype, "batch_per_gpu": a.batch, "hipgraph": graphed,
@@ -75,6 +79,6 @@ if rank == 0:
                                            "whole step; the step is bound by its many small BatchNorm / element-wise "
                                            "launches, not by the matrix pipe (profiles/r02_train_*_kernel_stats)"}}))
     print("world %d (global batch %d): %.0f img/s" % (world, a.batch * world, a.batch * world / wall * 1e3))
-    print("train W32 b=%d/GPU %s%s: %.1f ms/step (device %.1f ms), %.0f img/s per GPU, loss %s after %d steps, peak mem %.1f GiB" % (
-        a.batch, a.dtype, " hipGraph replay" if graphed else "", wall, dev, a.batch / wall * 1e3, loss.cpu().numpy(), tr.step_count,
+    print("train %s W32 b=%d/GPU %s%s: %.1f ms/step (device %.1f ms), %.0f img/s per GPU, loss %s after %d steps, peak mem %.1f GiB" % (
+        a.model, a.batch, a.dtype, " hipGraph replay" if graphed else "", wall, dev, a.batch / wall * 1e3, loss.cpu().numpy(), tr.step_count,
         torch.cuda.max_memory_allocated() / 2**30))

@@ -62,6 +62,18 @@ class ConvOp(C.Structure):
     ]
 
 
+class PsaTrainArgs(C.Structure):
+    """struct udp_psa_train_args (include/udp_pose_hip.h): one PSA_s block of the training step."""
+    _fields_ = [("w", C.c_void_p * 9), ("dw", C.c_void_p * 9)] + [(k, C.c_void_p) for k in (
+        "x", "x1", "theta", "x2", "dx2", "dtheta", "dx1", "dx", "save")] + [("save_floats", C.c_size_t)] + [
+        (k, C.c_int32) for k in ("n", "h", "w_px", "c")]
+
+
+# the nine parameter tensors of udp_psa_train_args.w / .dw, in that order (conv_v_left runs through the conv kernels)
+PSA_TRAIN_KEYS = (".conv_q_right.weight", ".conv_v_right.weight", ".conv_up.0.weight", ".conv_up.0.bias",
+                  ".conv_up.1.weight", ".conv_up.1.bias", ".conv_up.3.weight", ".conv_up.3.bias", ".conv_q_left.weight")
+
+
 class UdpPoseError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("udp_pose_hip error %d: %s" % (code, msg))
@@ -139,6 +151,13 @@ _SIGS = {
                                 C.c_float, _P]),
     "udp_adam_coefficients": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, _P]),
     "udp_adam_step_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, _P, C.c_float, _P]),
+    # training of the polarized self-attention block (pose_hrnet_psa)
+    "udp_psa_train_save_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "udp_psa_train_fwd_pool": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),
+    "udp_psa_train_fwd_sp": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),
+    "udp_psa_train_bwd_sp": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),
+    "udp_psa_train_bwd_pool": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),
+    "udp_psa_train_bwd_params": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -249,8 +249,10 @@ class PoseHighResolutionNetHip(PoseNetHip):
                 sd[k] = torch.zeros(shape)
             elif len(shape) == 4:
                 sd[k] = torch.randn(shape) * 0.001
-            elif k.endswith(".weight") and (k[:-7] + ".running_mean") in shapes:
-                sd[k] = torch.ones(shape)                 # BatchNorm weight
+            elif k.endswith(".weight") and ((k[:-7] + ".running_mean") in shapes or k.endswith(".deattn.conv_up.1.weight")):
+                # BatchNorm weight; the attention block's nn.LayerNorm keeps its default (weight 1, bias 0):
+                # pose_hrnet_psa.py:473-490 re-initialises Conv2d / BatchNorm2d / ConvTranspose2d only
+                sd[k] = torch.ones(shape)
             else:
                 sd[k] = torch.zeros(shape)                # BatchNorm / conv bias
         if pretrained and os.path.isfile(pretrained):
@@ -274,14 +276,13 @@ class PoseHighResolutionNetHip(PoseNetHip):
     def trainer(self):
         """The HRNetTrainer over this model's weights (created on first use from the current state_dict)."""
         if self._trainer is None:
-            if self.psa:
-                raise NotImplementedError("pose_hrnet_psa: the training step does not cover the attention ops")
             if self._sd is None:
                 raise RuntimeError("load_state_dict() or init_weights() first")
             from .train import HRNetTrainer
             if self.device is None:
                 self.to("cuda")
-            self._trainer = HRNetTrainer(self.cfg, self._sd, device=self.device, dtype="bf16" if self.dtype == "bf16" else "f32")
+            self._trainer = HRNetTrainer(self.cfg, self._sd, device=self.device, dtype="bf16" if self.dtype == "bf16" else "f32",
+                                         psa=self.psa)
         return self._trainer
 
     def parameters(self):

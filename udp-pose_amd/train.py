@@ -62,8 +62,13 @@ class _Group:
 
 
 class HRNetTrainer:
-    def __init__(self, cfg, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, cfg, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, psa=False,
+                 bucket_elems=6 * 1024 * 1024):
+        """``psa``: the pose_hrnet_psa variant -- a PSA_s ("<block>.deattn.*") after relu(bn1) of every BasicBlock
+        (pose_hrnet_psa.py:37,49), trained through the udp_psa_train_* entry points.  ``bucket_elems``: gradient elements
+        per all-reduce bucket (the default is ~25 MB)."""
         from .model import _get
+        self.psa = bool(psa)
         self.extra = _get(cfg, "MODEL", "EXTRA")
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
@@ -73,7 +78,7 @@ class HRNetTrainer:
         self._tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
         self.lr, self.betas, self.eps = lr, betas, eps
         self.step_count = 0
-        shapes = hrnet_param_shapes(self.extra, self.num_joints, self.target_type)
+        shapes = hrnet_param_shapes(self.extra, self.num_joints, self.target_type, psa=self.psa)
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         missing = [k for k in shapes if k not in sd and not k.endswith("num_batches_tracked")]
         if missing:
@@ -102,6 +107,8 @@ class HRNetTrainer:
             s = shapes[k]
             if len(s) != 4:
                 continue
+            if ".deattn." in k and not k.endswith(".conv_v_left.weight"):
+                continue            # the attention block reads its small fp32 matrices as they are; only theta is a conv
             cout, cin, ks = s[0], s[1], s[2]
             fwd = torch.empty(ks * ks * _rup(cout, 32) * _rup(cin, 16) * esz, dtype=torch.uint8, device=self.device)
             dg = None
@@ -141,7 +148,7 @@ class HRNetTrainer:
         # gradient; a bucket is reduced as soon as the backward has written its last gradient, so the exchange
         # of the late layers' gradients runs under the backward of the early ones (DDP's overlap, which the
         # reference gets from RSN/exps/RSN18.coco/train.py:46-48 / nn.DataParallel's reducer)
-        self.bucket_elems = 6 * 1024 * 1024
+        self.bucket_elems = int(bucket_elems)
         self._buckets, self._bucket_of = [], {}
         lo, cnt = 0, 0
         for i, k in enumerate(self._keys):
@@ -451,12 +458,64 @@ class HRNetTrainer:
         self._tape.append((_Group(ys), backward, ops, [nm + ".weight" for nm in names]))
         return ys
 
+    def _psa(self, x, p):
+        """PSA_s `p` on x (PSA.py:190-269), train mode: pool + channel chain + scale (x -> x1), theta = the 1x1 conv
+        conv_v_left through `_conv` (its weight and input gradients come with it), spatial gate (x1, theta -> x2).
+        Three tape entries; the nine small parameter gradients are written by ONE launch behind the last backward
+        piece (side stream), so they are listed on that entry."""
+        L = _lib.lib()
+        if x.c != x.ck:
+            raise ValueError("%s: attention over %d channels (not a multiple of 16)" % (p, x.c))
+        nfl = L.udp_psa_train_save_floats(x.n, x.h, x.w, x.c)
+        if not nfl:
+            _lib.check(-3)
+        save = torch.empty(nfl, dtype=torch.float32, device=self.device)
+        keys = [p + k for k in _lib.PSA_TRAIN_KEYS]
+
+        def args(**ptrs):
+            a = _lib.PsaTrainArgs()
+            for i, k in enumerate(keys):
+                a.w[i], a.dw[i] = self._p(k), self._g(k)
+            a.save, a.save_floats = save.data_ptr(), nfl
+            a.n, a.h, a.w_px, a.c = x.n, x.h, x.w, x.c
+            for k, t in ptrs.items():
+                setattr(a, k, t.data_ptr())
+            return a
+        x1 = self._new(x.n, x.h, x.w, x.c)
+        _lib.check(L.udp_psa_train_fwd_pool(C.byref(args(x=x.buf, x1=x1.buf)), self._dt, self._stream()))
+
+        def bwd_pool():
+            had = x.grad
+            dx = self._like(x)
+            _lib.check(L.udp_psa_train_bwd_pool(C.byref(args(dx1=x1.grad, x=x.buf, dx=dx)), self._dt, self._stream()))
+            if had is None:
+                x.grad = dx
+            else:
+                _lib.check(L.udp_ew_accumulate(had.data_ptr(), dx.data_ptr(), x.n, x.h, x.w, x.ck, 0, 0, 0, self._dt,
+                                               self._stream()))
+            self._on_side(lambda: _lib.check(L.udp_psa_train_bwd_params(C.byref(args()), self._dt, self._stream())), save)
+        self._tape.append((x1, bwd_pool, save, keys))
+        theta = self._conv(x1, p + ".conv_v_left")
+        x2 = self._new(x.n, x.h, x.w, x.c)
+        _lib.check(L.udp_psa_train_fwd_sp(C.byref(args(x1=x1.buf, theta=theta.buf, x2=x2.buf)), self._dt, self._stream()))
+
+        def bwd_sp():
+            if x1.grad is not None or theta.grad is not None:
+                raise RuntimeError("%s: the attention block's inner maps have one consumer each" % p)
+            x1.grad, theta.grad = self._like(x1), self._like(theta)
+            _lib.check(L.udp_psa_train_bwd_sp(C.byref(args(dx2=x2.grad, x1=x1.buf, theta=theta.buf, dtheta=theta.grad,
+                                                           dx1=x1.grad)), self._dt, self._stream()))
+        self._tape.append((x2, bwd_sp, save, []))
+        return x2
+
     def _blocks_lockstep(self, xs, ps):
         """BasicBlock `ps[b]` on branch b, all branches at once: the convs stay one launch each, the two BatchNorms
         of the block run as multi-tensor calls over the branches."""
         nb = len(xs)
         c1 = self._convs_lockstep(xs, [q + ".conv1" for q in ps])
         t = self._bn_multi(c1, [q + ".bn1" for q in ps])
+        if self.psa:
+            t = [self._psa(t[b], ps[b] + ".deattn") for b in range(nb)]
         c2 = self._convs_lockstep(t, [q + ".conv2" for q in ps])
         return self._bn_multi(c2, [q + ".bn2" for q in ps], res=xs)
 
@@ -564,6 +623,8 @@ class HRNetTrainer:
     # ------------------------------------------------------------------ the HRNet graph (pose_hrnet.py)
     def _basic(self, x, p):
         t = self._bn(self._conv(x, p + ".conv1", bn_stats=True), p + ".bn1")
+        if self.psa:
+            t = self._psa(t, p + ".deattn")
         return self._bn(self._conv(t, p + ".conv2", bn_stats=True), p + ".bn2", res=x)
 
     def _bottleneck(self, x, p):
