@@ -36,7 +36,14 @@ def _adversarial(hm, k):
 
 
 # ------------------------------------------------------------------ fused conv
-def _conv_case(dtype, ks, stride, cin, cout, h, w, n, relu, res, nup, nchw_out=False, seed=0):
+POISON = -12345.0      # exact in every storage mode; never a conv result here
+
+
+def _conv_case(dtype, ks, stride, cin, cout, h, w, n, relu, res, nup, nchw_out=False, seed=0, in_view=None, out_view=None,
+               res_view=None):
+    """``in_view`` / ``out_view`` / ``res_view`` = (coff, pitch): the operand is a channel slice of a wider tensor
+    (udp_conv_op.in_coff ...).  The wide input and residual are NaN outside the slice (a NaN that reaches the output
+    shows), the wide output is POISON outside its slice and must stay so, bit for bit."""
     rng = np.random.Generator(np.random.PCG64(seed))
     tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
     ws = dtype == "f16x2-ws"          # split fp16 on the weight-stationary kernel (fragment-major weights)
@@ -65,10 +72,16 @@ def _conv_case(dtype, ks, stride, cin, cout, h, w, n, relu, res, nup, nchw_out=F
     wp[:, :cout] = wt.permute(2, 3, 0, 1).reshape(ks * ks, cout, cin)
     bp = torch.zeros(cout_pad)
     bp[:cout] = bias
-    nhwc = lambda t: (f16x2.encode(t.permute(0, 2, 3, 1)) if h2 else t.permute(0, 2, 3, 1).contiguous()).cuda()
+    def nhwc(t, view=None):
+        t = t.permute(0, 2, 3, 1)
+        if view is not None:                                           # the slice inside a wider NaN tensor
+            wide = torch.full(t.shape[:3] + (view[1],), float("nan"), dtype=t.dtype)
+            wide[..., view[0]:view[0] + t.shape[3]] = t
+            t = wide
+        return (f16x2.encode(t) if h2 else t.contiguous()).cuda()
     wsp, wexp = f16x2.pack_weights_ws(wp) if ws else (None, 0)
-    d_x, d_w, d_b = nhwc(x), (wsp if ws else f16x2.encode(wp) if h2 else wp).cuda(), bp.cuda()
-    d_r = nhwc(r) if r is not None else None
+    d_x, d_w, d_b = nhwc(x, in_view), (wsp if ws else f16x2.encode(wp) if h2 else wp).cuda(), bp.cuda()
+    d_r = nhwc(r, res_view) if r is not None else None
     d_u = [nhwc(t) for t in ups] + [None] * (3 - nup)
     op = _lib.ConvOp()
     op.kind, op.ks, op.stride, op.relu = _lib.UDP_OP_CONV, ks, stride, int(relu)
@@ -78,18 +91,35 @@ def _conv_case(dtype, ks, stride, cin, cout, h, w, n, relu, res, nup, nchw_out=F
     op.wfmt, op.wexp = int(ws), wexp
     for u in range(nup):
         op.up_shift[u] = u + 1
+    if in_view:
+        op.in_coff, op.in_pitch = in_view
+    if res_view:
+        op.res_coff, op.res_pitch = res_view
+    ocoff, opitch = out_view or (0, cout)
+    if out_view:
+        op.out_coff, op.out_pitch = out_view
     if nchw_out:
         op.out_buf = _lib.UDP_BUF_OUTPUT
         out = torch.full((n, cout, ho, wo), float("nan"), dtype=torch.float32, device="cuda")
     elif h2:
-        out = torch.full((n, ho, wo, 2, cout), float("nan"), dtype=torch.float16, device="cuda")
+        out = torch.full((n, ho, wo, 2, opitch), float("nan"), dtype=torch.float16, device="cuda")
     else:
-        out = torch.full((n, ho, wo, cout), float("nan"), dtype=tdt, device="cuda")
+        out = torch.full((n, ho, wo, opitch), float("nan"), dtype=tdt, device="cuda")
+    if out_view:
+        out[...] = POISON
+        out[..., ocoff:ocoff + cout] = float("nan")
+        before = out.clone()
     _lib.check(_lib.lib().udp_conv2d_fused(C.byref(op), _lib.DTYPES[dtype], n,
                                            _lib.ptr(d_x), _lib.ptr(d_w), _lib.ptr(d_b), _lib.ptr(d_r),
                                            _lib.ptr(d_u[0]), _lib.ptr(d_u[1]), _lib.ptr(d_u[2]), _lib.ptr(out),
                                            _lib.stream_ptr()))
     torch.cuda.synchronize()
+    if out_view:
+        keep = torch.ones(opitch, dtype=torch.bool, device="cuda")
+        keep[ocoff:ocoff + cout] = False
+        bits = lambda t: t[..., keep].contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+        assert torch.equal(bits(out), bits(before)), "the conv wrote outside its output slice"
+        out = out[..., ocoff:ocoff + cout]
     got = (f16x2.decode(out) if h2 and not nchw_out else out.float()).cpu()
     if not nchw_out:
         got = got.permute(0, 3, 1, 2)
@@ -120,6 +150,8 @@ CONV_CASES = [
     (3, 1, 64, 64, 32, 24, 7, False, True, 0),     # no ReLU, residual, odd image count
     (3, 1, 192, 192, 24, 18, 3, True, True, 0),    # W48 branch 2 (6 K chunks, ragged row tiles)
     (3, 1, 384, 384, 12, 9, 5, True, True, 0),     # W48 branch 3 (12 K chunks, two cout blocks per tile)
+    (1, 2, 64, 128, 16, 12, 3, False, False, 0),   # 1x1 stride 2 (RSN downsample shortcut)
+    (1, 2, 32, 64, 9, 7, 2, True, False, 0),       # 1x1 stride 2 on odd sizes
 ]
 
 
@@ -137,6 +169,31 @@ def test_fused_conv_matches_torch_fp32(case, dtype):
     np.testing.assert_allclose(got, ref, rtol=0, atol=tol)
     if dtype.startswith("f16x2"):
         assert np.abs(got - ref).max() <= 2e-5 * scale, np.abs(got - ref).max()
+
+
+VIEW_CASES = [
+    # (ks, stride, cin, cout, h, w, n, relu, res, nup), in_view, out_view, res_view   -- views are (coff, pitch)
+    ((3, 1, 32, 32, 16, 12, 3, True, True, 0), (32, 64), (32, 96), (16, 64)),
+    ((1, 1, 64, 64, 9, 7, 3, True, False, 0), None, (64, 128), None),
+    ((3, 2, 64, 32, 16, 16, 3, True, False, 0), (64, 128), (0, 64), None),
+    ((3, 1, 32, 32, 16, 12, 3, True, False, 0), (32, 128), (96, 128), None),      # RSN's 26 -> 32 padded group (cin = cout = 32)
+]
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f16x2", "f16x2-ws", "bf16"])
+@pytest.mark.parametrize("case,in_view,out_view,res_view", VIEW_CASES, ids=lambda c: None if c is None or len(c) == 2 else "k%ds%d_%d-%d_%dx%d_n%d" % c[:7])
+def test_fused_conv_channel_views(case, in_view, out_view, res_view, dtype):
+    """Channel-slice views on UDP_OP_CONV: the result equals the dense conv's (same gate as
+    test_fused_conv_matches_torch_fp32), nothing outside the output slice is written (checked inside _conv_case),
+    and the NaN in the unread input / residual channels does not reach the output."""
+    got, ref = _conv_case(dtype, *case, in_view=in_view, out_view=out_view, res_view=res_view, seed=3)
+    assert not np.isnan(got).any(), "output slice not fully written, or an unread NaN channel reached it"
+    scale = max(1.0, float(np.abs(ref).max()))
+    err = float(np.abs(got - ref).max())
+    print("views %s %s: err %.3g" % (dtype, case[:6], err))
+    np.testing.assert_allclose(got, ref, rtol=0, atol=6e-3 * scale if dtype == "bf16" else 1e-4 * scale)
+    if dtype.startswith("f16x2"):
+        assert err <= 2e-5 * scale, err
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f16x2", "bf16"])
