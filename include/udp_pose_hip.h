@@ -96,7 +96,40 @@ enum udp_op_kind {
    * bias folded into `bias`), laid out as a 16-tap conv: wfmt 0 (UDP_F32) fp32 [pt][cout_pad][cin]; wfmt 1
    * (UDP_F16X2, required there) the fragment-major blocks described at `wfmt` with tap = pt, scaled by 2^wexp
    * (udp_pose_amd.f16x2.pack_deconv_weights_ws builds it). */
-  UDP_OP_DECONV = 11
+  UDP_OP_DECONV = 11,
+  /* Depthwise Conv2d(C, C, 3, stride, 1, groups=C, bias=False) + folded BatchNorm (+ ReLU if `relu`): the dw convs of
+   * the ShuffleV2 units (deep_hrnet/lib/models/backbones/shufflenetv2.py:54-55, :66-67; the reference never puts a
+   * ReLU behind one, the field is honoured all the same).  Per image, NHWC, UDP_F32 and UDP_F16X2 (UDP_BF16:
+   * UDP_ERR_UNSUPPORTED).  ks = 3, stride 1 | 2, cin == cout == cout_pad = C, a multiple of 32; any hin, win >= 1;
+   * hout = (hin - 1) / stride + 1, wout alike (integer division).  in_coff / in_pitch / out_coff / out_pitch are
+   * honoured (multiples of 8).  No addends, no group, wfmt 0.
+   * Weights: fp32 [9][C], tap-major (tap = 3 ky + kx), the BatchNorm scale folded in (in fp64 on the host), in EVERY
+   * storage mode; bias fp32 [C].
+   * Arithmetic per output element, fp32: acc = bias; then for ky = 0..2, kx = 0..2 in that order
+   * acc = fmaf(x[stride*oy + ky - 1][stride*ox + kx - 1], w[3 ky + kx], acc), where a tap outside the image is
+   * skipped (not read, not multiplied by zero).  UDP_F16X2 inputs are decoded hi + lo * 2^-11 first and the result is
+   * split again on store, with the udp_f16x2_overflow range guard.  A memory-bound VALU kernel: no MFMA.
+   *
+   * Shuffle passthrough (n_out2 = 1, stride 1 only).  A stride-1 ShuffleV2 unit (shufflenetv2.py:77-92) keeps the
+   * even logical channels of its input as x_proj and runs branch_main on the odd ones; its output is
+   * cat(x_proj, branch_main).  Unit tensors hold 2r logical channels as two halves of C stored channels each, the r
+   * real ones first and C - r zeros behind them: logical channel j lives at j (j < r) or C + j - r.  The dw launch of
+   * the unit copies x_proj while it is at it:
+   *   source       `res`:  res_buf, res_coff, res_pitch (>= res_coff + 2C) -- the unit's input, same h x w as the output
+   *   destination  out2_buf[0], out2_coff[0], out2_pitch[0] (>= out2_coff[0] + C) -- the first half of the unit's output
+   *   chain_cout = r, the real channels per half (even, 2 <= r <= C)
+   *   dst[k] = src[2k < r ? 2k : C + 2k - r] for k < r, and 0 for r <= k < C.
+   * It is a selection of stored bit patterns (both planes in UDP_F16X2), never decoded: bit for bit.  add2_* are not
+   * read.  udp_conv2d_fused: the source is `res`, the destination (written) is `up0`.  Without a passthrough
+   * (n_out2 = 0) res_buf must be UDP_BUF_NONE and chain_cout 0. */
+  UDP_OP_DWCONV = 12,
+  /* nn.PixelShuffle(2) on NHWC (deep_hrnet/lib/models/decoders/DUC.py:21,27), UDP_F32 and UDP_F16X2.  cin = 4 cout,
+   * cout % 8 == 0, hout = 2 hin, wout = 2 win; views honoured.  PyTorch takes out[c][2h+i][2w+j] from input channel
+   * 4c + 2i + j; here the PRODUCER (the DUC conv, through its output-channel permutation) stores that channel at
+   * (2i + j) * cout + c, so the four sub-pixel groups are contiguous per pixel and the op copies channels
+   * [g * cout, (g + 1) * cout) of pixel (h, w), g = 2i + j, to pixel (2h + i, 2w + j).  Pure data movement of the
+   * stored bit patterns: bit for bit, no weights / bias (may be NULL), no ReLU. */
+  UDP_OP_PIXSHUF = 13
 };
 
 #define UDP_MAX_LANES 4
@@ -198,8 +231,9 @@ int udp_hrnet_num_launches(const udp_hrnet* h);
 double udp_hrnet_flops_per_image(const udp_hrnet* h);
 
 /* One fused conv launch on raw pointers (the operator the program above is made of; used by
- * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE or
- * UDP_OP_DECONV: NHWC in / out, weights as documented there, no res / up), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
+ * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE,
+ * UDP_OP_DECONV, UDP_OP_DWCONV or UDP_OP_PIXSHUF: NHWC in / out, weights as documented there, no res / up -- except the
+ * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
  * its buffer ids and blob offsets are ignored except out_buf == UDP_BUF_OUTPUT, which selects
  * the NCHW fp32 output form.  in/res/ups/out: NHWC `dtype`; weights [ks*ks][cout_pad][cin]
  * `dtype`; bias fp32 [cout_pad].  Replaces conv+BN(+add)(+ReLU), pose_hrnet.py:43-59.

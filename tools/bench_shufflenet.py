@@ -1,0 +1,148 @@
+"""pose_shufflenetv2_10x_pixel_shuffle (1.0x, 256x192) throughput on one MI355X: batch 64 with the flip test and the DARK
+decode, split-fp16 ("f16x2") and fp32 storage.  Prints ONE JSON line: images/s, ms per step, launches per forward, the
+per-op-class kernel time of udp_hrnet_profile (hipEvents around every launch, eager) and, for the depthwise kernel,
+the achieved bytes/s on its algorithmic traffic (one read and one write of the map) next to the launch time of a
+UDP_OP_FUSE (an existing kernel that moves the same bytes) on a tensor of the same size, in the same session.
+
+    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
+
+from udp_pose_amd import _lib, synth                                        # noqa: E402
+from udp_pose_amd.inference import decode_device                            # noqa: E402
+from udp_pose_amd.model import MODELS                                       # noqa: E402
+from udp_pose_amd.synth_shufflenet import synth_shufflenet_state_dict       # noqa: E402
+from udp_pose_amd.transforms import COCO_FLIP_PAIRS, flip_fuse              # noqa: E402
+
+NAME = "pose_shufflenetv2_10x_pixel_shuffle"
+EXTRA = {"START_CHANNELS": 256, "ARCHITECTURE": (512, 256, 128), "MODEL_SIZE": "1.0x", "FINAL_CONV_KERNEL": 1}
+
+
+def op_class(name, kind, ks, stride):
+    if kind == _lib.UDP_OP_DWCONV:
+        return "dwconv_s%d" % stride
+    if kind == _lib.UDP_OP_PIXSHUF:
+        return "pixel_shuffle"
+    if kind == _lib.UDP_OP_STEM:
+        return "stem"
+    if kind == _lib.UDP_OP_MAXPOOL:
+        return "maxpool"
+    if name == "final_layer":
+        return "head"
+    return "conv%dx%d" % (ks, ks)
+
+
+def _window(fn, reps):
+    """Milliseconds per call of one timed window of ``reps`` calls (device events around the window)."""
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(reps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / reps
+
+
+def _samples(fns, reps, samples=7, warm=20):
+    """``samples`` timed windows per function, the functions ALTERNATING window by window (other work shares the host
+    and the chip: a drift hits all of them alike) -> per function (median, min, max) ms per call."""
+    for fn in fns:
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(samples):
+        for k, fn in enumerate(fns):
+            ts[k].append(_window(fn, reps))
+    return [(float(np.median(t)), min(t), max(t)) for t in ts]
+
+
+def dw_vs_fuse(dtype, images, c=128, h=32, w=24):
+    """One stride-1 depthwise launch (the stage-2 map of the 1.0x net: 2 x 64 stored channels) against one UDP_OP_FUSE
+    launch (out = relu(in)) on a tensor of the same size; both read the map once and write it once."""
+    lib, dt = _lib.lib(), _lib.DTYPES[dtype]
+    elems = images * h * w * c
+    a = torch.randn(elems, device="cuda").to(torch.float32)                 # 4 bytes per element in both modes
+    b = torch.empty_like(a)
+    wt, bias = torch.randn(9 * c, device="cuda"), torch.randn(c, device="cuda")
+    op = _lib.ConvOp()
+    op.kind, op.ks, op.stride, op.cin, op.cout, op.cout_pad = _lib.UDP_OP_DWCONV, 3, 1, c, c, c
+    op.hin, op.win, op.hout, op.wout = h, w, h, w
+    fu = _lib.ConvOp()
+    fu.kind, fu.ks, fu.stride, fu.relu, fu.cin, fu.cout, fu.cout_pad = _lib.UDP_OP_FUSE, 1, 1, 1, c, c, c
+    fu.hin, fu.win, fu.hout, fu.wout = h, w, h, w
+    if dtype == "f16x2":
+        a.view(torch.float16).fill_(0.5)
+    s = _lib.stream_ptr()
+    run = lambda o, wp, bp: _lib.check(lib.udp_conv2d_fused(C.byref(o), dt, images, _lib.ptr(a), wp, bp, None, None, None, None, _lib.ptr(b), s))
+    (ms_dw, dw_lo, dw_hi), (ms_fu, fu_lo, fu_hi) = _samples(
+        [lambda: run(op, _lib.ptr(wt), _lib.ptr(bias)), lambda: run(fu, None, None)], reps=300)
+    nbytes = 2.0 * elems * 4
+    return {"shape": [images, h, w, c], "windows": "7 alternating windows of 300 launches each",
+            "dw_us": round(ms_dw * 1e3, 2), "dw_us_min_max": [round(dw_lo * 1e3, 2), round(dw_hi * 1e3, 2)],
+            "fuse_us": round(ms_fu * 1e3, 2), "fuse_us_min_max": [round(fu_lo * 1e3, 2), round(fu_hi * 1e3, 2)],
+            "dw_over_fuse": round(ms_dw / ms_fu, 3), "dw_gbytes_per_s": round(nbytes / ms_dw / 1e6, 1),
+            "fuse_gbytes_per_s": round(nbytes / ms_fu / 1e6, 1)}
+
+
+def run(dtype, n, steps, warmup):
+    cfg = {"MODEL": {"NAME": NAME, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian", "EXTRA": EXTRA}}
+    sd = synth_shufflenet_state_dict(seed=7)
+    net = MODELS[NAME](cfg, is_train=False, dtype=dtype).load_state_dict(sd).to("cuda").eval()
+    x = torch.from_numpy(synth.synth_crops(n, 256, 192, seed=3)).cuda()
+    c, s = synth.synth_center_scale(n, seed=1)
+    c, s = torch.from_numpy(c.astype(np.float64)).cuda(), torch.from_numpy(s.astype(np.float64)).cuda()
+
+    def step():
+        raw = net.raw_forward(x, flip_test=True)
+        hm = flip_fuse(raw[:n], raw[n:], COCO_FLIP_PAIRS, False)
+        return decode_device(hm, c, s, "gaussian", True, 4.0, True)
+
+    (ms, ms_lo, ms_hi), = _samples([step], reps=steps, samples=5, warm=warmup)
+    handle, _, prog = net._compiled[(256, 192)]
+    lib = _lib.lib()
+    net.profile(x, flip_test=True)
+    ms_op, desc = net.profile(x, flip_test=True)           # second run: warm caches, kernels loaded
+    classes = {}
+    for (name, kind, ks, stride, cin, cout, hout, wout), t in zip(desc, ms_op):
+        e = classes.setdefault(op_class(name, kind, ks, stride), {"launches": 0, "ms": 0.0})
+        e["launches"] += 1
+        e["ms"] += float(t)
+    total = sum(e["ms"] for e in classes.values())
+    for e in classes.values():
+        e["share"] = round(e["ms"] / total, 4)
+        e["ms"] = round(e["ms"], 4)
+    return {"dtype": dtype, "images_per_s": round(n / ms * 1000.0, 1), "ms_per_step": round(ms, 3),
+            "ms_per_step_min_max": [round(ms_lo, 3), round(ms_hi, 3)], "windows": "5 windows of %d steps, median" % steps,
+            "launches_per_forward": int(lib.udp_hrnet_num_launches(handle)),
+            "gflop_per_image": round(lib.udp_hrnet_flops_per_image(handle) / 1e9, 3),
+            "kernel_ms_profiled": round(total, 3), "by_class": classes, "dwconv_vs_fuse": dw_vs_fuse(dtype, 2 * n)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--dtypes", default="f16x2,f32")
+    a = ap.parse_args()
+    res = [run(d, a.batch, a.steps, a.warmup) for d in a.dtypes.split(",")]
+    out = {"workload": "pose_shufflenetv2_10x_pixel_shuffle 1.0x 256x192 flip-test + DARK decode", "batch": a.batch, "results": res}
+    if len(res) == 2:
+        out["f16x2_over_f32"] = round(res[0]["images_per_s"] / res[1]["images_per_s"], 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

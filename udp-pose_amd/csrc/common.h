@@ -134,6 +134,13 @@ int ws_set_stamps(unsigned long long* dev_buf);      // diagnostic builds (-DUDP
 // deconv.hip: ConvTranspose2d(k=4, s=2, p=1) + folded BatchNorm (+ ReLU), UDP_OP_DECONV (fp32 and split fp16)
 int describe_deconv(ConvParams p, int dtype, Launch* out);
 int deconv_h2_overflow(hipStream_t s, int reset, int* flag);
+// dwconv.hip: depthwise 3x3 conv + folded BatchNorm with the ShuffleV2 passthrough (UDP_OP_DWCONV), PixelShuffle(2)
+// (UDP_OP_PIXSHUF); the *_validate functions hold the field rules of udp_pose_hip.h for both entry points
+int dwconv_validate(const udp_conv_op& o, int dtype);
+int pixshuf_validate(const udp_conv_op& o, int dtype);
+int describe_dwconv(ConvParams p, int dtype, int stride, Launch* out);
+int describe_pixshuf(ConvParams p, int dtype, Launch* out);
+int dwconv_h2_overflow(hipStream_t s, int reset, int* flag);
 int conv_h2_overflow(hipStream_t s, int reset, int* flag);       // conv.hip / conv_ws.hip / psa.hip: their g_h2_overflow
 int conv_ws_h2_overflow(hipStream_t s, int reset, int* flag);
 int psa_h2_overflow(hipStream_t s, int reset, int* flag);

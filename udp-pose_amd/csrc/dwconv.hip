@@ -1,0 +1,322 @@
+// Depthwise 3x3 conv + folded BatchNorm (UDP_OP_DWCONV) and PixelShuffle(2) (UDP_OP_PIXSHUF) for gfx950 (MI355X):
+// the two ops of pose_shufflenetv2_10x_pixel_shuffle that the conv kernels do not cover
+// (deep_hrnet/lib/models/backbones/shufflenetv2.py:54-55, :66-67; decoders/DUC.py:21).
+//
+// A depthwise conv has no GEMM in it (9 MACs per output element): it is memory-bound and runs on the VALU.  Lanes run
+// along the channels -- a thread owns V consecutive channels (fp32: 4 = one 16-byte load; split fp16: 8 = one 16-byte
+// load per plane of the [C hi][C lo] pixel) of one output column and walks DOWN a strip of output rows, so a wave
+// reads 64 * 16 contiguous bytes of a pixel (row) at a time.  Vertical reuse is in registers:
+//   stride 1: three accumulators are in flight (the output rows iy-1, iy, iy+1 that input row iy feeds with ky = 2,
+//             1, 0); an input row is loaded once per strip and leaves with the accumulator it completes;
+//   stride 2: input row 2oy+1 is kept for the next output row (its ky = 0 taps), rows 2oy are used once.
+// A strip of R output rows loads R + 2 (stride 2: 2R + 1) input rows, so neighbouring strips re-read their halo rows:
+// (R + 2) / R of the input per launch -- 1x only when one strip covers the image, 2x at the floor R = 2 that
+// describe_dwconv reaches when a small launch needs the threads more than the reuse.
+// The three columns of a row are loaded by the thread itself; the neighbouring columns' threads sit in the same
+// workgroup and read the same lines at about the same time, so that 3x is expected to hit the L1 / L2 (not measured
+// with counters; NOTES.md has the achieved bytes/s against an element-wise kernel moving the same map).  Per output
+// element the arithmetic is: bias, then nine fmaf in the order ky, kx -- whatever the strip height, so the result
+// does not depend on the launch geometry.  Taps outside the image are SKIPPED (never read, never multiplied by 0).
+//
+// The shuffle passthrough of a stride-1 ShuffleV2 unit (shufflenetv2.py:77-92) rides in the same launch: the thread
+// that stores output pixel (n, y, x), channels c..c+V-1 also copies the V selected channels of the unit's input to
+// the unit's output (udp_pose_hip.h, UDP_OP_DWCONV).  A selection: bit patterns are moved, never decoded.
+#include "conv_dev.h"
+
+namespace udp {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
+
+template <typename T>
+struct DwTr;
+template <>
+struct DwTr<float> {
+  static constexpr int V = 4, PL = 1;
+  using E = uint32_t;      // one stored unit of a plane
+  using Vec = u32x4;       // 16 bytes of them
+};
+template <>
+struct DwTr<H2> {
+  static constexpr int V = 8, PL = 2;
+  using E = uint16_t;
+  using Vec = u16x8;
+};
+
+// V consecutive channels from `c` of pixel `pix` of the input view, decoded to fp32
+template <typename T, int V>
+__device__ __forceinline__ void dw_load(const ConvParams& p, size_t pix, int c, float (&x)[V]) {
+  if constexpr (std::is_same<T, float>::value) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.in) + pix * (size_t)p.in_pitch + p.in_coff + c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = v[k];
+  } else {
+    const _Float16* q = reinterpret_cast<const _Float16*>(p.in) + pix * (2 * (size_t)p.in_pitch) + p.in_coff + c;
+    const f16x8 hi = *reinterpret_cast<const f16x8*>(q), lo = *reinterpret_cast<const f16x8*>(q + p.in_pitch);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = (float)hi[k] + (float)lo[k] * kLoInv;    // lo * 2^-11 is exact
+  }
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void dw_store(const ConvParams& p, size_t pix, int c, const float (&a)[V]) {
+  float v[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) v[k] = p.relu ? __builtin_fmaxf(a[k], 0.f) : a[k];
+  if constexpr (std::is_same<T, float>::value) {
+    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + pix * (size_t)p.out_pitch + p.out_coff + c) = f32x4{v[0], v[1], v[2], v[3]};
+  } else {
+    f16x8 hi, lo;
+    h2_split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);     // raises the range flag
+    _Float16* q = reinterpret_cast<_Float16*>(p.out) + pix * (2 * (size_t)p.out_pitch) + p.out_coff + c;
+    *reinterpret_cast<f16x8*>(q) = hi;
+    *reinterpret_cast<f16x8*>(q + p.out_pitch) = lo;
+  }
+}
+
+// the three taps of kernel row KY on one input row; v0 / v2: the left / right column lies inside the image
+template <int KY, int V>
+__device__ __forceinline__ void dw_row(float (&acc)[V], const float (&x)[3][V], const float (&w)[9][V], bool v0, bool v2) {
+  if (v0) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = __builtin_fmaf(x[0][k], w[3 * KY][k], acc[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < V; ++k) acc[k] = __builtin_fmaf(x[1][k], w[3 * KY + 1][k], acc[k]);
+  if (v2) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = __builtin_fmaf(x[2][k], w[3 * KY + 2][k], acc[k]);
+  }
+}
+
+// Shuffle passthrough: destination channels c..c+V-1 (of cin) of pixel `pix` take the even logical channels of the
+// source.  The source pixel holds 2r logical channels as two halves of cin (= Cp) stored channels, r real ones
+// first: logical j sits at j (j < r) or Cp + j - r.  Destination k < r takes logical 2k, k >= r is zero.
+template <typename T>
+__device__ __forceinline__ void dw_passthrough(const ConvParams& p, size_t pix, int c) {
+  using E = typename DwTr<T>::E;
+  using Vec = typename DwTr<T>::Vec;
+  constexpr int V = DwTr<T>::V, PL = DwTr<T>::PL;
+  const int r = p.up_shift[0], Cp = p.Cin;
+#pragma unroll
+  for (int pl = 0; pl < PL; ++pl) {
+    const E* src = reinterpret_cast<const E*>(p.res) + pix * ((size_t)PL * p.res_pitch) + (size_t)pl * p.res_pitch + p.res_coff;
+    E* dst = reinterpret_cast<E*>(p.out2[0]) + pix * ((size_t)PL * p.out2_pitch[0]) + (size_t)pl * p.out2_pitch[0] + p.out2_coff[0] + c;
+    Vec o;
+    if (2 * c + 2 * V <= r) {           // the whole span lies in the first half: two aligned 16-byte loads
+      const Vec a = *reinterpret_cast<const Vec*>(src + 2 * c), b = *reinterpret_cast<const Vec*>(src + 2 * c + V);
+#pragma unroll
+      for (int e = 0; e < V / 2; ++e) {
+        o[e] = a[2 * e];
+        o[V / 2 + e] = b[2 * e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const int k = c + e, j = 2 * k;
+        o[e] = k < r ? src[j < r ? j : Cp + j - r] : (E)0;
+      }
+    }
+    *reinterpret_cast<Vec*>(dst) = o;
+  }
+}
+
+// thread = (image, row strip, output column, channel group); p.R output rows per strip, p.tiles_y strips per image,
+// p.ntiles threads in all
+template <typename T, int S>
+__global__ __launch_bounds__(256) void dwconv3_kernel(const ConvParams p) {
+  constexpr int V = DwTr<T>::V;
+  long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)p.ntiles) return;
+  const int cgs = p.Cin / V;
+  const int c = (int)(idx % cgs) * V;
+  idx /= cgs;
+  const int ox = (int)(idx % p.Wout);
+  idx /= p.Wout;
+  const int st = (int)(idx % p.tiles_y);
+  const int n = (int)(idx / p.tiles_y);
+  const int oy0 = st * p.R;
+  const int oy1 = oy0 + p.R < p.Hout ? oy0 + p.R : p.Hout;
+
+  float w[9][V], b[V];
+  const float* wg = reinterpret_cast<const float*>(p.wgt);
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int q = 0; q < V; q += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(wg + (size_t)t * p.Cin + c + q);
+      w[t][q] = v[0], w[t][q + 1] = v[1], w[t][q + 2] = v[2], w[t][q + 3] = v[3];
+    }
+#pragma unroll
+  for (int q = 0; q < V; q += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p.bias + c + q);
+    b[q] = v[0], b[q + 1] = v[1], b[q + 2] = v[2], b[q + 3] = v[3];
+  }
+
+  const int ix0 = ox * S - 1;                       // column of tap kx = 0; kx = 1 is always inside
+  const bool v0 = ix0 >= 0, v2 = ix0 + 2 < p.Win;
+  const size_t img_in = (size_t)n * p.Hin * p.Win, img_out = (size_t)n * p.Hout * p.Wout;
+  auto load_row = [&](int iy, float (&x)[3][V]) __attribute__((always_inline)) {
+    const size_t pix = img_in + (size_t)iy * p.Win + ox * S;      // the centre column
+#pragma unroll
+    for (int k = 0; k < V; ++k) x[0][k] = x[2][k] = 0.f;          // never used when outside (dw_row skips the tap)
+    if (v0) dw_load<T, V>(p, pix - 1, c, x[0]);
+    dw_load<T, V>(p, pix, c, x[1]);
+    if (v2) dw_load<T, V>(p, pix + 1, c, x[2]);
+  };
+  auto finish = [&](int oy, const float (&a)[V]) __attribute__((always_inline)) {
+    const size_t pix = img_out + (size_t)oy * p.Wout + ox;
+    dw_store<T, V>(p, pix, c, a);
+    if (p.nout2) dw_passthrough<T>(p, pix, c);
+  };
+
+  if constexpr (S == 1) {
+    float a0[V], a1[V], a2[V];                      // output rows iy-1 (ky = 2 next), iy (ky = 1), iy+1 (ky = 0)
+#pragma unroll
+    for (int k = 0; k < V; ++k) a0[k] = a1[k] = a2[k] = b[k];
+    for (int iy = oy0 - 1; iy <= oy1; ++iy) {
+      if (iy >= 0 && iy < p.Hin) {
+        float x[3][V];
+        load_row(iy, x);
+        dw_row<2, V>(a0, x, w, v0, v2);
+        dw_row<1, V>(a1, x, w, v0, v2);
+        dw_row<0, V>(a2, x, w, v0, v2);
+      }
+      if (iy - 1 >= oy0) finish(iy - 1, a0);        // (iy - 1 < oy1 by the loop bound)
+#pragma unroll
+      for (int k = 0; k < V; ++k) a0[k] = a1[k], a1[k] = a2[k], a2[k] = b[k];
+    }
+  } else {
+    float xp[3][V];                                 // input row 2oy-1: ky = 2 of row oy-1, ky = 0 of row oy
+    bool have = 2 * oy0 - 1 >= 0;
+    if (have) load_row(2 * oy0 - 1, xp);
+    for (int oy = oy0; oy < oy1; ++oy) {
+      float a[V], x[3][V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) a[k] = b[k];
+      if (have) dw_row<0, V>(a, xp, w, v0, v2);
+      load_row(2 * oy, x);                          // 2oy <= Hin - 1 by hout = (hin - 1) / 2 + 1
+      dw_row<1, V>(a, x, w, v0, v2);
+      have = 2 * oy + 1 < p.Hin;
+      if (have) {
+        load_row(2 * oy + 1, xp);
+        dw_row<2, V>(a, xp, w, v0, v2);
+      }
+      finish(oy, a);
+    }
+  }
+}
+
+// PixelShuffle(2) on NHWC with the four sub-pixel groups contiguous per pixel: group g = 2i + j (cout channels from
+// g * cout) of input pixel (h, w) -> output pixel (2h + i, 2w + j).  thread = (image, h, w, g, channel group).
+template <typename T>
+__global__ __launch_bounds__(256) void pixshuf2_kernel(const ConvParams p) {
+  using E = typename DwTr<T>::E;
+  using Vec = typename DwTr<T>::Vec;
+  constexpr int V = DwTr<T>::V, PL = DwTr<T>::PL;
+  long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)p.ntiles) return;
+  const int cgs = p.Cout / V;
+  const int c = (int)(idx % cgs) * V;
+  idx /= cgs;
+  const int g = (int)(idx & 3);
+  idx >>= 2;
+  const int x = (int)(idx % p.Win);
+  idx /= p.Win;
+  const int y = (int)(idx % p.Hin);
+  const int n = (int)(idx / p.Hin);
+  const size_t pin = ((size_t)n * p.Hin + y) * p.Win + x;
+  const size_t pout = ((size_t)n * p.Hout + 2 * y + (g >> 1)) * p.Wout + 2 * x + (g & 1);
+#pragma unroll
+  for (int pl = 0; pl < PL; ++pl) {
+    const E* src = reinterpret_cast<const E*>(p.in) + pin * ((size_t)PL * p.in_pitch) + (size_t)pl * p.in_pitch + p.in_coff + g * p.Cout + c;
+    E* dst = reinterpret_cast<E*>(p.out) + pout * ((size_t)PL * p.out_pitch) + (size_t)pl * p.out_pitch + p.out_coff + c;
+    *reinterpret_cast<Vec*>(dst) = *reinterpret_cast<const Vec*>(src);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+// Shape / field rules of the two kinds (udp_pose_hip.h), shared by udp_hrnet_create and udp_conv2d_fused.
+int dwconv_validate(const udp_conv_op& o, int dtype) {
+  if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: storage modes f32 and f16x2 only");
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "depthwise conv: dtype %d", dtype);
+  if (o.ks != 3 || (o.stride != 1 && o.stride != 2) || o.cin <= 0 || o.cin != o.cout || o.cin % 32 || o.cout_pad != o.cout)
+    return fail(UDP_ERR_ARG, "depthwise conv: 3x3, stride 1 | 2, cin == cout == cout_pad, a multiple of 32 (C%d->%d)", o.cin, o.cout);
+  if (o.hin < 1 || o.win < 1 || o.hout != (o.hin - 1) / o.stride + 1 || o.wout != (o.win - 1) / o.stride + 1)
+    return fail(UDP_ERR_ARG, "depthwise conv: %dx%d -> %dx%d does not match stride %d", o.hin, o.win, o.hout, o.wout, o.stride);
+  const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
+  if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
+    return fail(UDP_ERR_ARG, "depthwise conv: channel views");
+  if (o.n_up || o.group || o.in_stuff2 || o.wfmt || o.out_buf == UDP_BUF_OUTPUT)
+    return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: no addends, groups or NCHW output; weights fp32 [9][C] (wfmt 0)");
+  if (o.n_out2 == 0) {
+    if (o.chain_cout) return fail(UDP_ERR_ARG, "depthwise conv: chain_cout without a passthrough (n_out2 = 1)");
+    return UDP_OK;
+  }
+  // shuffle passthrough
+  const int r = o.chain_cout, rpitch = o.res_pitch, dpitch = o.out2_pitch[0];
+  if (o.n_out2 != 1 || o.stride != 1) return fail(UDP_ERR_ARG, "depthwise conv: the passthrough is one second output of a stride-1 launch");
+  if (r < 2 || r > o.cin || (r & 1)) return fail(UDP_ERR_ARG, "depthwise conv: passthrough of %d real channels per half of %d", r, o.cin);
+  if (o.res_coff < 0 || o.res_coff + 2 * o.cin > rpitch || o.out2_coff[0] < 0 || o.out2_coff[0] + o.cin > dpitch ||
+      (o.res_coff | rpitch | o.out2_coff[0] | dpitch) % 8)
+    return fail(UDP_ERR_ARG, "depthwise conv: passthrough views (res: 2 x %d channels, out2[0]: %d channels, pitches given)", o.cin, o.cin);
+  return UDP_OK;
+}
+
+int pixshuf_validate(const udp_conv_op& o, int dtype) {
+  if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: storage modes f32 and f16x2 only");
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "pixel shuffle: dtype %d", dtype);
+  if (o.cout <= 0 || o.cout % 8 || o.cin != 4 * o.cout || o.hin < 1 || o.win < 1 || o.hout != 2 * o.hin || o.wout != 2 * o.win)
+    return fail(UDP_ERR_ARG, "pixel shuffle: C%d %dx%d -> C%d %dx%d (cin = 4 cout, cout %% 8 == 0, output = 2x the input)", o.cin, o.hin,
+                o.win, o.cout, o.hout, o.wout);
+  const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
+  if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
+    return fail(UDP_ERR_ARG, "pixel shuffle: channel views");
+  if (o.n_up || o.n_out2 || o.chain_cout || o.group || o.in_stuff2 || o.relu || o.out_buf == UDP_BUF_OUTPUT)
+    return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: pure data movement (no addends, ReLU, second outputs or NCHW output)");
+  return UDP_OK;
+}
+
+// p: geometry, views, in / out / wgt / bias set; passthrough: nout2 = 1, res, res_pitch / res_coff, out2[0],
+// out2_pitch[0] / out2_coff[0], up_shift[0] = real channels per half.
+int describe_dwconv(ConvParams p, int dtype, int stride, Launch* out) {
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: storage modes f32 and f16x2 only");
+  if (!p.in || !p.out || !p.wgt || !p.bias || (p.nout2 && (!p.res || !p.out2[0])) || (!p.nout2 && p.res))
+    return fail(UDP_ERR_ARG, "depthwise conv: null pointer (or a residual without a passthrough)");
+  const int V = dtype == UDP_F32 ? 4 : 8;
+  const long per_row = (long)p.N * p.Wout * (p.Cin / V);
+  // rows per strip: the whole height if that still fills the chip (256 CUs x 8 waves), else halved down to 2
+  int R = p.Hout;
+  while (R > 2 && per_row * ((p.Hout + R - 1) / R) < 131072) R = (R + 1) / 2;
+  p.R = R;
+  p.tiles_y = (p.Hout + R - 1) / R;
+  const long total = per_row * p.tiles_y;
+  if (total <= 0 || total >= (1L << 31) - 256) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: %ld threads; split the batch", total);
+  p.ntiles = (int)total;
+  out->fn = dtype == UDP_F32 ? (stride == 1 ? reinterpret_cast<const void*>(&dwconv3_kernel<float, 1>) : reinterpret_cast<const void*>(&dwconv3_kernel<float, 2>))
+                             : (stride == 1 ? reinterpret_cast<const void*>(&dwconv3_kernel<H2, 1>) : reinterpret_cast<const void*>(&dwconv3_kernel<H2, 2>));
+  out->grid = dim3((unsigned)((total + 255) / 256));
+  out->block = dim3(256);
+  out->lds = 0;
+  out->p = p;
+  return UDP_OK;
+}
+
+int describe_pixshuf(ConvParams p, int dtype, Launch* out) {
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: storage modes f32 and f16x2 only");
+  if (!p.in || !p.out) return fail(UDP_ERR_ARG, "pixel shuffle: null pointer");
+  const int V = dtype == UDP_F32 ? 4 : 8;
+  const long total = (long)p.N * p.Hin * p.Win * 4 * (p.Cout / V);
+  if (total <= 0 || total >= (1L << 31) - 256) return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: %ld threads; split the batch", total);
+  p.ntiles = (int)total;
+  out->fn = dtype == UDP_F32 ? reinterpret_cast<const void*>(&pixshuf2_kernel<float>) : reinterpret_cast<const void*>(&pixshuf2_kernel<H2>);
+  out->grid = dim3((unsigned)((total + 255) / 256));
+  out->block = dim3(256);
+  out->lds = 0;
+  out->p = p;
+  return UDP_OK;
+}
+
+int dwconv_h2_overflow(hipStream_t s, int reset, int* flag) { return h2_overflow_fetch(s, reset, flag); }
+
+}  // namespace udp

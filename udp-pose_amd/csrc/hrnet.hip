@@ -60,7 +60,7 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
   const int nb = (int)h->buf_elems.size();
   auto buf_ok = [&](int b, int64_t need) { return b >= 0 && b < nb && h->buf_elems[b] >= need; };
   const int64_t out_need = (int64_t)o.hout * o.wout * (o.out_pitch ? o.out_pitch : o.cout);
-  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_DECONV) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_PIXSHUF) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
   if (o.lane < 0 || o.lane >= UDP_MAX_LANES || o.n_wait < 0 || o.n_wait > UDP_MAX_WAIT) return fail(UDP_ERR_ARG, "op %d: lane/n_wait", idx);
   for (int k = 0; k < o.n_wait; ++k)
     if (o.wait_op[k] < 0 || o.wait_op[k] >= idx) return fail(UDP_ERR_ARG, "op %d: wait_op %d must name an earlier op", idx, o.wait_op[k]);
@@ -96,6 +96,27 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
     if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15) || o.b_off < 0 ||
         (size_t)o.b_off + (size_t)o.cout_pad * 4 > h->weights_bytes || (o.b_off & 15) || o.wexp < -40 || o.wexp > 40)
       return fail(UDP_ERR_ARG, "op %d: deconv weight / bias range outside the blob or misaligned", idx);
+    return UDP_OK;
+  }
+  if (o.kind == UDP_OP_DWCONV || o.kind == UDP_OP_PIXSHUF) {
+    // depthwise 3x3 conv + folded BatchNorm (+ the ShuffleV2 passthrough) / PixelShuffle(2) (dwconv.hip)
+    const bool dw = o.kind == UDP_OP_DWCONV;
+    const int rc = dw ? dwconv_validate(o, h->dtype) : pixshuf_validate(o, h->dtype);
+    if (rc) return rc;
+    const int ipitch = o.in_pitch ? o.in_pitch : o.cin;
+    if (!buf_ok(o.in_buf, (int64_t)o.hin * o.win * ipitch) || !buf_ok(o.out_buf, out_need) || o.in_buf == o.out_buf)
+      return fail(UDP_ERR_ARG, "op %d: %s buffers missing, too small or aliased", idx, dw ? "depthwise conv" : "pixel shuffle");
+    if (dw && o.n_out2) {
+      const int64_t hw = (int64_t)o.hout * o.wout;
+      const int d = o.out2_buf[0];
+      if (!buf_ok(o.res_buf, hw * o.res_pitch) || !buf_ok(d, hw * o.out2_pitch[0]) || d == o.in_buf || d == o.out_buf || d == o.res_buf)
+        return fail(UDP_ERR_ARG, "op %d: depthwise conv: passthrough buffers missing, too small or aliased", idx);
+    } else if (o.res_buf != UDP_BUF_NONE) {
+      return fail(UDP_ERR_UNSUPPORTED, "op %d: %s takes no residual", idx, dw ? "depthwise conv" : "pixel shuffle");
+    }
+    if (dw && (o.w_off < 0 || (size_t)o.w_off + (size_t)9 * o.cin * 4 > h->weights_bytes || (o.w_off & 15) || o.b_off < 0 ||
+               (size_t)o.b_off + (size_t)o.cin * 4 > h->weights_bytes || (o.b_off & 15)))
+      return fail(UDP_ERR_ARG, "op %d: depthwise conv weight / bias range outside the blob or misaligned", idx);
     return UDP_OK;
   }
   if (o.kind >= UDP_OP_PSA_POOL) {
@@ -212,6 +233,7 @@ extern "C" int udp_f16x2_overflow(void* stream, int reset) {
   if (!rc) rc = conv_ws_h2_overflow(s, reset, &flag);
   if (!rc) rc = psa_h2_overflow(s, reset, &flag);
   if (!rc) rc = deconv_h2_overflow(s, reset, &flag);
+  if (!rc) rc = dwconv_h2_overflow(s, reset, &flag);
   return rc ? rc : flag;
 }
 
@@ -254,6 +276,7 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
       h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;
     if (ops[i].kind == UDP_OP_BLOCK) h->flops += 2 * 2.0 * 9 * 32 * 32 * ops[i].hout * ops[i].wout;
     if (ops[i].kind == UDP_OP_DECONV) h->flops += 2.0 * 4 * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;   // 2x2 taps per output pixel
+    if (ops[i].kind == UDP_OP_DWCONV) h->flops += 2.0 * 9 * ops[i].cout * ops[i].hout * ops[i].wout;   // 9 MACs per output element
     if (ops[i].kind == UDP_OP_CONV && ops[i].chain_cout) h->flops += 2.0 * ops[i].cout * ops[i].chain_cout * ops[i].hout * ops[i].wout;
     h->ops.push_back(ops[i]);
   }
@@ -358,13 +381,13 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
     p.nout2 = o.n_out2;
     for (int k = 0; k < o.n_out2; ++k) {
       p.out2[k] = buf(o.out2_buf[k]);
-      p.add2[k] = buf(o.add2_buf[k]);
+      p.add2[k] = o.kind == UDP_OP_DWCONV ? nullptr : buf(o.add2_buf[k]);    // (the passthrough reads `res`)
       p.out2_coff[k] = o.out2_coff[k];
       p.out2_pitch[k] = o.out2_pitch[k] ? o.out2_pitch[k] : o.cout;
       p.add2_coff[k] = o.add2_coff[k];
       p.add2_pitch[k] = o.add2_pitch[k] ? o.add2_pitch[k] : o.cout;
     }
-    if (is_stem || o.kind == UDP_OP_CONV || o.kind == UDP_OP_DECONV) {
+    if (is_stem || o.kind == UDP_OP_CONV || o.kind == UDP_OP_DECONV || o.kind == UDP_OP_DWCONV) {
       p.wgt = h->weights + o.w_off;
       p.bias = reinterpret_cast<const float*>(h->weights + o.b_off);
     }
@@ -376,6 +399,7 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       p.up_shift[1] = o.chain_wexp;
       p.up_shift[2] = o.chain_relu;
     }
+    if (o.kind == UDP_OP_DWCONV) p.up_shift[0] = o.chain_cout;   // passthrough: real channels per half (n_up == 0)
     if (o.kind == UDP_OP_BLOCK) {
       p.wgt = h->weights + o.w_off;
       p.bias = reinterpret_cast<const float*>(h->weights + o.b_off);
@@ -398,6 +422,8 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       case UDP_OP_MAXPOOL: rc = describe_maxpool(p, h->dtype, &ls[i]); break;
       case UDP_OP_BILINEAR: rc = describe_bilinear(p, h->dtype, &ls[i]); break;
       case UDP_OP_DECONV: rc = describe_deconv(p, h->dtype, &ls[i]); break;
+      case UDP_OP_DWCONV: rc = describe_dwconv(p, h->dtype, o.stride, &ls[i]); break;
+      case UDP_OP_PIXSHUF: rc = describe_pixshuf(p, h->dtype, &ls[i]); break;
       default:
         if (o.chain_cout) {
           rc = describe_conv_chain(p, &ls[i]);
@@ -732,8 +758,17 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (!o || !in || !out) return fail(UDP_ERR_ARG, "udp_conv2d_fused: null pointer");
   if (dtype != UDP_F32 && dtype != UDP_BF16 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "udp_conv2d_fused: dtype %d", dtype);
   if (n <= 0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: n=%d", n);
-  if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV) return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
-  if (o->kind != UDP_OP_FUSE && (!weights || !bias)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV && o->kind != UDP_OP_DWCONV && o->kind != UDP_OP_PIXSHUF)
+    return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
+  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && (!weights || !bias)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind == UDP_OP_DWCONV || o->kind == UDP_OP_PIXSHUF) {
+    const bool dw = o->kind == UDP_OP_DWCONV;
+    const int rc = dw ? dwconv_validate(*o, dtype) : pixshuf_validate(*o, dtype);
+    if (rc) return rc;
+    // the passthrough of a depthwise launch: source = `res`, destination = `up0` (written)
+    const bool pass = dw && o->n_out2 == 1;
+    if (pass ? (!res || !up0) : (res != nullptr)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: %s: res / up0 are the passthrough's source / destination (n_out2 = 1) and NULL otherwise", dw ? "depthwise conv" : "pixel shuffle");
+  }
   if (o->kind == UDP_OP_DECONV) {
     if (o->ks != 4 || o->stride != 2 || o->hout != 2 * o->hin || o->wout != 2 * o->win)
       return fail(UDP_ERR_ARG, "udp_conv2d_fused: deconv must be k4 s2 p1 (output = 2x the input)");
@@ -758,8 +793,18 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   p.Cout = o->cout;
   p.CoutPad = o->cout_pad;
   p.relu = o->relu;
-  if (o->n_out2) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused: second outputs (n_out2) exist in udp_hrnet programs only");
-  if (o->chain_cout) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused: chained convs (chain_cout) exist in udp_hrnet programs only");
+  if (o->kind == UDP_OP_DWCONV) {
+    if (o->n_out2) {
+      p.nout2 = 1;
+      p.out2[0] = const_cast<void*>(up0);
+      p.out2_coff[0] = o->out2_coff[0];
+      p.out2_pitch[0] = o->out2_pitch[0];
+      p.up_shift[0] = o->chain_cout;
+    }
+  } else {
+    if (o->n_out2) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused: second outputs (n_out2) exist in udp_hrnet programs only");
+    if (o->chain_cout) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused: chained convs (chain_cout) exist in udp_hrnet programs only");
+  }
   p.wfmt = o->wfmt;
   p.wexp = o->wexp;
   p.in_stuff2 = o->in_stuff2 ? 1 : 0;
@@ -799,6 +844,8 @@ static int conv2d_fused_impl(const udp_conv_op* o, int dtype, int n, const void*
   p.bn_ws = bn_ws;
   const int rc = o->kind == UDP_OP_FUSE     ? describe_fuse(p, dtype, &l)
                  : o->kind == UDP_OP_DECONV ? describe_deconv(p, dtype, &l)
+                 : o->kind == UDP_OP_DWCONV ? describe_dwconv(p, dtype, o->stride, &l)
+                 : o->kind == UDP_OP_PIXSHUF ? describe_pixshuf(p, dtype, &l)
                                             : describe_conv(p, dtype, o->ks, o->stride, &l);
   if (rc) return rc;
   if (bn_ws) {

@@ -388,4 +388,45 @@ def get_pose_net_resnet(cfg, is_train, **kwargs):
     return PoseResNetHip(cfg, **kwargs)
 
 
-MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet}
+class PoseShuffleNetV2Hip(PoseNetHip):
+    """pose_shufflenetv2_10x_pixel_shuffle (deep_hrnet/lib/models/pose_shufflenetv2_10x_pixel_shuffle.py:23-53: the
+    ShuffleNetV2 0.5x / 1.0x / 1.5x backbone, the pixel-shuffle (DUC) decoder, ``final_layer``) inference through the
+    same C ABI; ``state_dict`` in the reference module's key format.  Storage modes "f32" and "f16x2" (the depthwise
+    kernel has no bf16 form)."""
+
+    NAME = "pose_shufflenetv2_10x_pixel_shuffle"
+    DTYPES = ("f32", "f16x2")
+
+    def __init__(self, cfg, dtype="f32"):
+        from .shufflenet_plan import shufflenet_spec
+        if dtype not in self.DTYPES:
+            raise ValueError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
+        super().__init__(cfg, dtype)
+        self.extra = _get(cfg, "MODEL", "EXTRA")
+        self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
+        self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
+        self.spec = shufflenet_spec(self.extra, self.num_joints, self.target_type)   # NotImplementedError for 2.0x ...
+
+    def param_shapes(self):
+        from .synth_shufflenet import shufflenet_param_shapes
+        sp = self.spec
+        return shufflenet_param_shapes(model_size=sp["model_size"], num_joints=self.num_joints, target_type=self.target_type,
+                                       start_channels=sp["start_channels"], architecture=sp["architecture"],
+                                       final_kernel=sp["final_kernel"])
+
+    def init_weights(self, pretrained=""):
+        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+
+    def _make_program(self, h, w):
+        from .shufflenet_plan import ShuffleNetV2Program
+        return ShuffleNetV2Program(self._sd, self.spec, h, w, self.dtype)
+
+
+def get_pose_net_shufflenetv2(cfg, is_train, **kwargs):
+    """pose_shufflenetv2_10x_pixel_shuffle.py:56-65 (``get_pose_net``); inference only -- the weights come from
+    ``load_state_dict`` (the reference loads ImageNet weights under is_train; training is out of scope)."""
+    return PoseShuffleNetV2Hip(cfg, **kwargs)
+
+
+MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet,
+          "pose_shufflenetv2_10x_pixel_shuffle": get_pose_net_shufflenetv2}
