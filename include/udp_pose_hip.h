@@ -97,16 +97,18 @@ enum udp_op_kind {
    * (UDP_F16X2, required there) the fragment-major blocks described at `wfmt` with tap = pt, scaled by 2^wexp
    * (udp_pose_amd.f16x2.pack_deconv_weights_ws builds it). */
   UDP_OP_DECONV = 11,
-  /* Depthwise Conv2d(C, C, 3, stride, 1, groups=C, bias=False) + folded BatchNorm (+ ReLU if `relu`): the dw convs of
-   * the ShuffleV2 units (deep_hrnet/lib/models/backbones/shufflenetv2.py:54-55, :66-67; the reference never puts a
-   * ReLU behind one, the field is honoured all the same).  Per image, NHWC, UDP_F32 and UDP_F16X2 (UDP_BF16:
-   * UDP_ERR_UNSUPPORTED).  ks = 3, stride 1 | 2, cin == cout == cout_pad = C, a multiple of 32; any hin, win >= 1;
+  /* Depthwise Conv2d(C, C, ks, stride, ks / 2, groups=C, bias=False) + folded BatchNorm (+ ReLU if `relu` == 1;
+   * activation code 2 is refused): the dw convs of the ShuffleV2 units (deep_hrnet/lib/models/backbones/
+   * shufflenetv2.py:54-55, :66-67; the reference never puts a ReLU behind one, the field is honoured all the same) and
+   * the 5x5 / 7x7 ones of ShuffleNetV2+ (backbones/shufflenetv2_plus.py:97, :119).  Per image, NHWC, UDP_F32 and
+   * UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED).  ks = 3 | 5 | 7 (anything else: UDP_ERR_ARG), stride 1 | 2,
+   * cin == cout == cout_pad = C, a multiple of 32; any hin, win >= 1;
    * hout = (hin - 1) / stride + 1, wout alike (integer division).  in_coff / in_pitch / out_coff / out_pitch are
    * honoured (multiples of 8).  No addends, no group, wfmt 0.
-   * Weights: fp32 [9][C], tap-major (tap = 3 ky + kx), the BatchNorm scale folded in (in fp64 on the host), in EVERY
-   * storage mode; bias fp32 [C].
-   * Arithmetic per output element, fp32: acc = bias; then for ky = 0..2, kx = 0..2 in that order
-   * acc = fmaf(x[stride*oy + ky - 1][stride*ox + kx - 1], w[3 ky + kx], acc), where a tap outside the image is
+   * Weights: fp32 [ks * ks][C], tap-major (tap = ks * ky + kx), the BatchNorm scale folded in (in fp64 on the host),
+   * in EVERY storage mode; bias fp32 [C].
+   * Arithmetic per output element, fp32: acc = bias; then for ky = 0..ks-1, kx = 0..ks-1 in that order
+   * acc = fmaf(x[stride*oy + ky - ks/2][stride*ox + kx - ks/2], w[ks ky + kx], acc), where a tap outside the image is
    * skipped (not read, not multiplied by zero).  UDP_F16X2 inputs are decoded hi + lo * 2^-11 first and the result is
    * split again on store, with the udp_f16x2_overflow range guard.  A memory-bound VALU kernel: no MFMA.
    *
@@ -129,8 +131,31 @@ enum udp_op_kind {
    * (2i + j) * cout + c, so the four sub-pixel groups are contiguous per pixel and the op copies channels
    * [g * cout, (g + 1) * cout) of pixel (h, w), g = 2i + j, to pixel (2h + i, 2w + j).  Pure data movement of the
    * stored bit patterns: bit for bit, no weights / bias (may be NULL), no ReLU. */
-  UDP_OP_PIXSHUF = 13
+  UDP_OP_PIXSHUF = 13,
+  /* Squeeze-and-excitation (SELayer, deep_hrnet/lib/models/backbones/shufflenetv2_plus.py:34-60) on an NHWC view of
+   * C stored channels, UDP_F32 and UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED); one launch, one workgroup per image:
+   *   mean[c] = (1 / HW) sum_p in[p][c]          h = relu(W1 mean + b1)   (BatchNorm folded into W1 / b1)
+   *   m[c] = clamp((W2 h)[c] + 3, 0, 6) / 6      out[p][c] = in[p][c] * m[c]
+   * cin == cout == cout_pad = C, a multiple of 32 up to 512; hout == hin, wout == win (any size >= 1);
+   * chain_cout = the hidden width Ch (rows of W1), 1 <= Ch <= min(256, C) -- the way it carries r for the passthrough
+   * of UDP_OP_DWCONV; no chained conv.  in_coff / in_pitch / out_coff / out_pitch are honoured (multiples of 8, as
+   * for kinds 12 and 13).  `out` MAY be `in` (same buffer, same view): the pool is complete before the first store
+   * and every element is read and written by one thread; any other overlap of the two is refused.  relu must be 0;
+   * no addends, second outputs, group, wfmt.  Parameter block at w_off (udp_conv2d_fused: `weights`; `bias` may be
+   * NULL), fp32 in EVERY storage mode: W1 transposed [C][Ch], b1 [Ch], W2 transposed [Ch][C].  Pad channels carry
+   * zero weights: m = 0.5 there and the stored zeros stay exact zeros.  All sums are fp32 in a fixed order that
+   * depends on (C, Ch, HW) only, nothing is atomic: an image's result does not depend on the batch it arrives in. */
+  UDP_OP_SE = 14
 };
+
+/* udp_conv_op.relu is an activation code.  UDP_ACT_HSWISH: v * (clamp(v + 3, 0, 6) / 6) in fp32, applied where the
+ * ReLU is applied, before the value is stored -- in UDP_OP_STEM and in a 1x1 stride-1 UDP_OP_CONV writing NHWC
+ * without addends (res / up), second outputs, a chain or a group, in UDP_F32 and UDP_F16X2 (wfmt 0 and 1, channel
+ * views honoured).  Every other op and conv form answers it with UDP_ERR_UNSUPPORTED; a code outside 0..2 is
+ * UDP_ERR_ARG. */
+#define UDP_ACT_NONE 0
+#define UDP_ACT_RELU 1
+#define UDP_ACT_HSWISH 2
 
 #define UDP_MAX_LANES 4
 #define UDP_MAX_WAIT 8
@@ -139,8 +164,8 @@ enum udp_op_kind {
 
 typedef struct udp_conv_op {
   int32_t kind;            /* enum udp_op_kind */
-  int32_t ks, stride;      /* kernel size 1|3 (pad = ks/2), stride 1|2 */
-  int32_t relu;            /* apply ReLU in the epilogue */
+  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7; pad = ks/2), stride 1|2 */
+  int32_t relu;            /* activation of the epilogue: UDP_ACT_NONE / UDP_ACT_RELU / UDP_ACT_HSWISH (see there) */
   int32_t cin, cout;       /* real channel counts (cin multiple of 16 for UDP_OP_CONV) */
   int32_t cout_pad;        /* cout rounded up to a multiple of 32: rows of `weights`/`bias` */
   int32_t hin, win, hout, wout;
@@ -232,8 +257,8 @@ double udp_hrnet_flops_per_image(const udp_hrnet* h);
 
 /* One fused conv launch on raw pointers (the operator the program above is made of; used by
  * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE,
- * UDP_OP_DECONV, UDP_OP_DWCONV or UDP_OP_PIXSHUF: NHWC in / out, weights as documented there, no res / up -- except the
- * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
+ * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF or UDP_OP_SE: NHWC in / out, weights as documented there, no res / up -- except the
+ * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`; UDP_OP_SE: `weights` = the parameter block, chain_cout = hidden width), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
  * its buffer ids and blob offsets are ignored except out_buf == UDP_BUF_OUTPUT, which selects
  * the NCHW fp32 output form.  in/res/ups/out: NHWC `dtype`; weights [ks*ks][cout_pad][cin]
  * `dtype`; bias fp32 [cout_pad].  Replaces conv+BN(+add)(+ReLU), pose_hrnet.py:43-59.

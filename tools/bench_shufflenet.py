@@ -4,7 +4,11 @@ per-op-class kernel time of udp_hrnet_profile (hipEvents around every launch, ea
 the achieved bytes/s on its algorithmic traffic (one read and one write of the map) next to the launch time of a
 UDP_OP_FUSE (an existing kernel that moves the same bytes) on a tensor of the same size, in the same session.
 
-    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32]
+    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32] [--model v2|plus]
+
+``--model plus``: pose_shufflenetv2_plus_pixel_shuffle (Small) instead, with the same measurements; its depthwise
+launches are classed by kernel size, and the squeeze-excitation launches and the 1x1 convs with the hard-swish
+epilogue get classes of their own.
 """
 import argparse
 import ctypes as C
@@ -27,6 +31,8 @@ from udp_pose_amd.transforms import COCO_FLIP_PAIRS, flip_fuse              # no
 
 NAME = "pose_shufflenetv2_10x_pixel_shuffle"
 EXTRA = {"START_CHANNELS": 256, "ARCHITECTURE": (512, 256, 128), "MODEL_SIZE": "1.0x", "FINAL_CONV_KERNEL": 1}
+PLUS_NAME = "pose_shufflenetv2_plus_pixel_shuffle"
+PLUS_EXTRA = dict(EXTRA, MODEL_SIZE="Small")
 
 
 def op_class(name, kind, ks, stride):
@@ -41,6 +47,18 @@ def op_class(name, kind, ks, stride):
     if name == "final_layer":
         return "head"
     return "conv%dx%d" % (ks, ks)
+
+
+def op_class_plus(op):
+    """Classes of the ShuffleNetV2+ program: as above, but depthwise launches by kernel size, UDP_OP_SE, and the 1x1
+    convs whose epilogue is the hard-swish."""
+    if op["kind"] == _lib.UDP_OP_DWCONV:
+        return "dwconv%d_s%d" % (op["ks"], op["stride"])
+    if op["kind"] == _lib.UDP_OP_SE:
+        return "se"
+    if op["kind"] == _lib.UDP_OP_CONV and op["relu"] == _lib.UDP_ACT_HSWISH:
+        return "conv1x1_hs"
+    return op_class(op["name"], op["kind"], op["ks"], op["stride"])
 
 
 def _window(fn, reps):
@@ -96,10 +114,15 @@ def dw_vs_fuse(dtype, images, c=128, h=32, w=24):
             "fuse_gbytes_per_s": round(nbytes / ms_fu / 1e6, 1)}
 
 
-def run(dtype, n, steps, warmup):
-    cfg = {"MODEL": {"NAME": NAME, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian", "EXTRA": EXTRA}}
-    sd = synth_shufflenet_state_dict(seed=7)
-    net = MODELS[NAME](cfg, is_train=False, dtype=dtype).load_state_dict(sd).to("cuda").eval()
+def run(dtype, n, steps, warmup, plus=False):
+    name = PLUS_NAME if plus else NAME
+    cfg = {"MODEL": {"NAME": name, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian", "EXTRA": PLUS_EXTRA if plus else EXTRA}}
+    if plus:
+        from udp_pose_amd.synth_shufflenet_plus import synth_shufflenet_plus_state_dict
+        sd = synth_shufflenet_plus_state_dict(seed=7)
+    else:
+        sd = synth_shufflenet_state_dict(seed=7)
+    net = MODELS[name](cfg, is_train=False, dtype=dtype).load_state_dict(sd).to("cuda").eval()
     x = torch.from_numpy(synth.synth_crops(n, 256, 192, seed=3)).cuda()
     c, s = synth.synth_center_scale(n, seed=1)
     c, s = torch.from_numpy(c.astype(np.float64)).cuda(), torch.from_numpy(s.astype(np.float64)).cuda()
@@ -115,8 +138,8 @@ def run(dtype, n, steps, warmup):
     net.profile(x, flip_test=True)
     ms_op, desc = net.profile(x, flip_test=True)           # second run: warm caches, kernels loaded
     classes = {}
-    for (name, kind, ks, stride, cin, cout, hout, wout), t in zip(desc, ms_op):
-        e = classes.setdefault(op_class(name, kind, ks, stride), {"launches": 0, "ms": 0.0})
+    for k, ((name, kind, ks, stride, cin, cout, hout, wout), t) in enumerate(zip(desc, ms_op)):
+        e = classes.setdefault(op_class_plus(prog._ops[k]) if plus else op_class(name, kind, ks, stride), {"launches": 0, "ms": 0.0})
         e["launches"] += 1
         e["ms"] += float(t)
     total = sum(e["ms"] for e in classes.values())
@@ -136,9 +159,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--dtypes", default="f16x2,f32")
+    ap.add_argument("--model", choices=("v2", "plus"), default="v2")
     a = ap.parse_args()
-    res = [run(d, a.batch, a.steps, a.warmup) for d in a.dtypes.split(",")]
-    out = {"workload": "pose_shufflenetv2_10x_pixel_shuffle 1.0x 256x192 flip-test + DARK decode", "batch": a.batch, "results": res}
+    plus = a.model == "plus"
+    res = [run(d, a.batch, a.steps, a.warmup, plus) for d in a.dtypes.split(",")]
+    workload = "pose_shufflenetv2_plus_pixel_shuffle Small" if plus else "pose_shufflenetv2_10x_pixel_shuffle 1.0x"
+    out = {"workload": workload + " 256x192 flip-test + DARK decode", "batch": a.batch, "results": res}
     if len(res) == 2:
         out["f16x2_over_f32"] = round(res[0]["images_per_s"] / res[1]["images_per_s"], 3)
     print(json.dumps(out))

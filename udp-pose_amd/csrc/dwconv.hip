@@ -1,6 +1,7 @@
 // Depthwise 3x3 conv + folded BatchNorm (UDP_OP_DWCONV) and PixelShuffle(2) (UDP_OP_PIXSHUF) for gfx950 (MI355X):
 // the two ops of pose_shufflenetv2_10x_pixel_shuffle that the conv kernels do not cover
-// (deep_hrnet/lib/models/backbones/shufflenetv2.py:54-55, :66-67; decoders/DUC.py:21).
+// (deep_hrnet/lib/models/backbones/shufflenetv2.py:54-55, :66-67; decoders/DUC.py:21).  Further down: the 5x5 / 7x7
+// depthwise form (dwconvk_kernel) and squeeze-and-excitation (UDP_OP_SE, se_kernel) of the ShuffleNetV2+ backbone.
 //
 // A depthwise conv has no GEMM in it (9 MACs per output element): it is memory-bound and runs on the VALU.  Lanes run
 // along the channels -- a thread owns V consecutive channels (fp32: 4 = one 16-byte load; split fp16: 8 = one 16-byte
@@ -207,6 +208,147 @@ __global__ __launch_bounds__(256) void dwconv3_kernel(const ConvParams p) {
   }
 }
 
+// Depthwise K x K, K = 5 | 7 (ShuffleNetV2+ units, backbones/shufflenetv2_plus.py:97, :119).  The register scheme of
+// dwconv3_kernel does not stretch: 49 taps x 8 channels of weights alone are 392 VGPRs.  Here a thread owns ONE
+// output pixel x V channels and holds ONE kernel row of weights (K x V <= 56 registers) at a time: the ky loop is
+// rolled, the kx loop unrolled; a tap costs PL input loads + V / 4 weight loads of 16 bytes, all of which hit the
+// L1 / L2 (the maps where K > 3 occurs are 64 x 48 and smaller, the weights K * K * C * 4 bytes).  Same arithmetic
+// contract as above: bias, then one fmaf per tap in the order ky, kx, taps outside the image skipped.
+// thread = (image, output row, output column, channel group); p.ntiles threads in all
+template <typename T, int S, int K>
+__global__ __launch_bounds__(256) void dwconvk_kernel(const ConvParams p) {
+  constexpr int V = DwTr<T>::V, PAD = K / 2;
+  long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)p.ntiles) return;
+  const int cgs = p.Cin / V;
+  const int c = (int)(idx % cgs) * V;
+  idx /= cgs;
+  const int ox = (int)(idx % p.Wout);
+  idx /= p.Wout;
+  const int oy = (int)(idx % p.Hout);
+  const int n = (int)(idx / p.Hout);
+  const float* wg = reinterpret_cast<const float*>(p.wgt) + c;
+  float a[V];
+#pragma unroll
+  for (int q = 0; q < V; q += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p.bias + c + q);
+    a[q] = v[0], a[q + 1] = v[1], a[q + 2] = v[2], a[q + 3] = v[3];
+  }
+  const int ix0 = ox * S - PAD;
+  const size_t img_in = (size_t)n * p.Hin * p.Win;
+#pragma unroll 1
+  for (int ky = 0; ky < K; ++ky) {
+    const int iy = oy * S - PAD + ky;
+    if (iy < 0 || iy >= p.Hin) continue;
+    const size_t row = img_in + (size_t)iy * p.Win;
+#pragma unroll
+    for (int kx = 0; kx < K; ++kx) {
+      const int ix = ix0 + kx;
+      if (ix >= 0 && ix < p.Win) {
+        float x[V], w[V];
+        dw_load<T, V>(p, row + ix, c, x);
+#pragma unroll
+        for (int q = 0; q < V; q += 4) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(wg + (size_t)(ky * K + kx) * p.Cin + q);
+          w[q] = v[0], w[q + 1] = v[1], w[q + 2] = v[2], w[q + 3] = v[3];
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) a[k] = __builtin_fmaf(x[k], w[k], a[k]);
+      }
+    }
+  }
+  const size_t pix = ((size_t)n * p.Hout + oy) * p.Wout + ox;
+  dw_store<T, V>(p, pix, c, a);
+  if (p.nout2) dw_passthrough<T>(p, pix, c);
+}
+
+// Squeeze-and-excitation (UDP_OP_SE; SELayer, backbones/shufflenetv2_plus.py:34-60) on an NHWC view of C = p.Cin
+// stored channels: one workgroup per image, four phases separated by barriers --
+//   1. mean[c] over the HW pixels: thread (pixel group g, channel group) adds pixels g, g + P, ... in that order,
+//      then the P partial sums of a channel are added in the order g = 0 .. P-1 and multiplied by 1 / HW;
+//   2. h[j] = relu(b1[j] + sum_c W1[c][j] mean[c]), j < Ch = p.up_shift[0]: the channel range is cut into Q equal
+//      parts, thread (part, j) runs its part with fmaf in channel order, the parts are added in order onto b1[j];
+//   3. m[c] = clamp(sum_j W2[j][c] h[j] + 3, 0, 6) / 6, fmaf from 0 in the order j = 0 .. Ch-1;
+//   4. out = in * m[c], every element by one thread.
+// P and Q depend on (C, Ch) only and nothing is atomic: an image's result does not depend on the batch, the lane
+// or graph replay.  The pool is complete before the first store, and an element is read and written by the same
+// thread, so `out` may be the very view `in` is.  Parameter block (fp32): W1 [C][Ch], b1 [Ch], W2 [Ch][C].
+// Dynamic LDS: (256 * V + 2 * C + 256 + Ch) floats.
+template <typename T>
+__global__ __launch_bounds__(256) void se_kernel(const ConvParams p) {
+  constexpr int V = DwTr<T>::V;
+  extern __shared__ __attribute__((aligned(16))) float se_s[];
+  const int C = p.Cin, Ch = p.up_shift[0], HW = p.Hin * p.Win;
+  float* part = se_s;                  // [P][C], P * C <= 256 * V
+  float* mean = part + 256 * V;        // [C]
+  float* mul = mean + C;               // [C]
+  float* hpart = mul + C;              // [Q][Ch], Q * Ch <= 256
+  float* hid = hpart + 256;            // [Ch]
+  const int tid = threadIdx.x;
+  const size_t img = (size_t)blockIdx.x * HW;
+  const int cgs = C / V;
+  const int P = 256 / cgs < HW ? 256 / cgs : HW;        // cgs <= 128 (dwconv_validate / se_validate: C <= 512)
+  {
+    const int cg = tid % cgs, g = tid / cgs;
+    if (g < P) {
+      float s[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) s[k] = 0.f;
+      for (int px = g; px < HW; px += P) {
+        float x[V];
+        dw_load<T, V>(p, img + px, cg * V, x);
+#pragma unroll
+        for (int k = 0; k < V; ++k) s[k] += x[k];
+      }
+#pragma unroll
+      for (int k = 0; k < V; ++k) part[g * C + cg * V + k] = s[k];
+    }
+  }
+  __syncthreads();
+  const float inv = 1.f / (float)HW;
+  for (int c = tid; c < C; c += 256) {
+    float s = part[c];
+    for (int g = 1; g < P; ++g) s += part[g * C + c];
+    mean[c] = s * inv;
+  }
+  __syncthreads();
+  const float* w1 = reinterpret_cast<const float*>(p.wgt);
+  const float* b1 = w1 + (size_t)C * Ch;
+  const float* w2 = b1 + Ch;
+  const int Q = 256 / Ch < C ? 256 / Ch : C;            // Ch <= 256
+  const int L = (C + Q - 1) / Q;
+  {
+    const int j = tid % Ch, q = tid / Ch;
+    if (q < Q) {
+      const int c1 = (q + 1) * L < C ? (q + 1) * L : C;
+      float s = 0.f;
+      for (int c = q * L; c < c1; ++c) s = __builtin_fmaf(w1[(size_t)c * Ch + j], mean[c], s);
+      hpart[q * Ch + j] = s;
+    }
+  }
+  __syncthreads();
+  if (tid < Ch) {
+    float s = b1[tid];
+    for (int q = 0; q < Q; ++q) s += hpart[q * Ch + tid];
+    hid[tid] = __builtin_fmaxf(s, 0.f);
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float s = 0.f;
+    for (int j = 0; j < Ch; ++j) s = __builtin_fmaf(w2[(size_t)j * C + c], hid[j], s);
+    mul[c] = __builtin_fminf(__builtin_fmaxf(s + 3.f, 0.f), 6.f) / 6.f;
+  }
+  __syncthreads();
+  for (int e = tid; e < HW * cgs; e += 256) {
+    const int cg = e % cgs, px = e / cgs;
+    float x[V];
+    dw_load<T, V>(p, img + px, cg * V, x);
+#pragma unroll
+    for (int k = 0; k < V; ++k) x[k] *= mul[cg * V + k];
+    dw_store<T, V>(p, img + px, cg * V, x);
+  }
+}
+
 // PixelShuffle(2) on NHWC with the four sub-pixel groups contiguous per pixel: group g = 2i + j (cout channels from
 // g * cout) of input pixel (h, w) -> output pixel (2h + i, 2w + j).  thread = (image, h, w, g, channel group).
 template <typename T>
@@ -240,15 +382,17 @@ __global__ __launch_bounds__(256) void pixshuf2_kernel(const ConvParams p) {
 int dwconv_validate(const udp_conv_op& o, int dtype) {
   if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: storage modes f32 and f16x2 only");
   if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "depthwise conv: dtype %d", dtype);
-  if (o.ks != 3 || (o.stride != 1 && o.stride != 2) || o.cin <= 0 || o.cin != o.cout || o.cin % 32 || o.cout_pad != o.cout)
-    return fail(UDP_ERR_ARG, "depthwise conv: 3x3, stride 1 | 2, cin == cout == cout_pad, a multiple of 32 (C%d->%d)", o.cin, o.cout);
+  if ((o.ks != 3 && o.ks != 5 && o.ks != 7) || (o.stride != 1 && o.stride != 2) || o.cin <= 0 || o.cin != o.cout || o.cin % 32 || o.cout_pad != o.cout)
+    return fail(UDP_ERR_ARG, "depthwise conv: 3x3 | 5x5 | 7x7, stride 1 | 2, cin == cout == cout_pad, a multiple of 32 (k%d C%d->%d)", o.ks, o.cin, o.cout);
+  if (o.relu < 0 || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "depthwise conv: activation code %d", o.relu);
+  if (o.relu == UDP_ACT_HSWISH) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: no hard-swish epilogue (activation code 2)");
   if (o.hin < 1 || o.win < 1 || o.hout != (o.hin - 1) / o.stride + 1 || o.wout != (o.win - 1) / o.stride + 1)
     return fail(UDP_ERR_ARG, "depthwise conv: %dx%d -> %dx%d does not match stride %d", o.hin, o.win, o.hout, o.wout, o.stride);
   const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
   if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
     return fail(UDP_ERR_ARG, "depthwise conv: channel views");
   if (o.n_up || o.group || o.in_stuff2 || o.wfmt || o.out_buf == UDP_BUF_OUTPUT)
-    return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: no addends, groups or NCHW output; weights fp32 [9][C] (wfmt 0)");
+    return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: no addends, groups or NCHW output; weights fp32 [ks * ks][C] (wfmt 0)");
   if (o.n_out2 == 0) {
     if (o.chain_cout) return fail(UDP_ERR_ARG, "depthwise conv: chain_cout without a passthrough (n_out2 = 1)");
     return UDP_OK;
@@ -263,6 +407,23 @@ int dwconv_validate(const udp_conv_op& o, int dtype) {
   return UDP_OK;
 }
 
+// UDP_OP_SE: cin == cout stored channels (a multiple of 32, at most 512), chain_cout = hidden width (1 .. 256)
+int se_validate(const udp_conv_op& o, int dtype) {
+  if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "squeeze-excitation: storage modes f32 and f16x2 only");
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "squeeze-excitation: dtype %d", dtype);
+  if (o.cin <= 0 || o.cin != o.cout || o.cin % 32 || o.cin > 512 || o.cout_pad != o.cout || o.chain_cout < 1 || o.chain_cout > 256 ||
+      o.chain_cout > o.cin || o.hin < 1 || o.win < 1 || o.hout != o.hin || o.wout != o.win)
+    return fail(UDP_ERR_ARG, "squeeze-excitation: cin == cout == cout_pad, a multiple of 32 up to 512, hidden width (chain_cout) 1 .. min(256, cin), "
+                "output = input size (C%d->%d, hidden %d)", o.cin, o.cout, o.chain_cout);
+  const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
+  if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
+    return fail(UDP_ERR_ARG, "squeeze-excitation: channel views");
+  if (o.relu < 0 || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "squeeze-excitation: activation code %d", o.relu);
+  if (o.n_up || o.n_out2 || o.group || o.in_stuff2 || o.wfmt || o.relu || o.out_buf == UDP_BUF_OUTPUT)
+    return fail(UDP_ERR_UNSUPPORTED, "squeeze-excitation: no addends, activation, second outputs, groups or NCHW output");
+  return UDP_OK;
+}
+
 int pixshuf_validate(const udp_conv_op& o, int dtype) {
   if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: storage modes f32 and f16x2 only");
   if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "pixel shuffle: dtype %d", dtype);
@@ -272,6 +433,7 @@ int pixshuf_validate(const udp_conv_op& o, int dtype) {
   const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
   if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
     return fail(UDP_ERR_ARG, "pixel shuffle: channel views");
+  if (o.relu < 0 || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "pixel shuffle: activation code %d", o.relu);
   if (o.n_up || o.n_out2 || o.chain_cout || o.group || o.in_stuff2 || o.relu || o.out_buf == UDP_BUF_OUTPUT)
     return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: pure data movement (no addends, ReLU, second outputs or NCHW output)");
   return UDP_OK;
@@ -279,11 +441,26 @@ int pixshuf_validate(const udp_conv_op& o, int dtype) {
 
 // p: geometry, views, in / out / wgt / bias set; passthrough: nout2 = 1, res, res_pitch / res_coff, out2[0],
 // out2_pitch[0] / out2_coff[0], up_shift[0] = real channels per half.
-int describe_dwconv(ConvParams p, int dtype, int stride, Launch* out) {
+int describe_dwconv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
   if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: storage modes f32 and f16x2 only");
   if (!p.in || !p.out || !p.wgt || !p.bias || (p.nout2 && (!p.res || !p.out2[0])) || (!p.nout2 && p.res))
     return fail(UDP_ERR_ARG, "depthwise conv: null pointer (or a residual without a passthrough)");
   const int V = dtype == UDP_F32 ? 4 : 8;
+  if (ks != 3) {      // 5x5 / 7x7: one output pixel x V channels per thread (dwconvk_kernel)
+    if ((ks != 5 && ks != 7) || (stride != 1 && stride != 2)) return fail(UDP_ERR_ARG, "depthwise conv: ks %d stride %d", ks, stride);
+    const long total = (long)p.N * p.Hout * p.Wout * (p.Cin / V);
+    if (total <= 0 || total >= (1L << 31) - 256) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: %ld threads; split the batch", total);
+    p.ntiles = (int)total;
+#define UDP_DWK(T, S, K) reinterpret_cast<const void*>(&dwconvk_kernel<T, S, K>)
+    out->fn = dtype == UDP_F32 ? (ks == 5 ? (stride == 1 ? UDP_DWK(float, 1, 5) : UDP_DWK(float, 2, 5)) : (stride == 1 ? UDP_DWK(float, 1, 7) : UDP_DWK(float, 2, 7)))
+                               : (ks == 5 ? (stride == 1 ? UDP_DWK(H2, 1, 5) : UDP_DWK(H2, 2, 5)) : (stride == 1 ? UDP_DWK(H2, 1, 7) : UDP_DWK(H2, 2, 7)));
+#undef UDP_DWK
+    out->grid = dim3((unsigned)((total + 255) / 256));
+    out->block = dim3(256);
+    out->lds = 0;
+    out->p = p;
+    return UDP_OK;
+  }
   const long per_row = (long)p.N * p.Wout * (p.Cin / V);
   // rows per strip: the whole height if that still fills the chip (256 CUs x 8 waves), else halved down to 2
   int R = p.Hout;
@@ -298,6 +475,20 @@ int describe_dwconv(ConvParams p, int dtype, int stride, Launch* out) {
   out->grid = dim3((unsigned)((total + 255) / 256));
   out->block = dim3(256);
   out->lds = 0;
+  out->p = p;
+  return UDP_OK;
+}
+
+// p: geometry, views, in / out, wgt = the parameter block, up_shift[0] = hidden width.  One workgroup per image.
+int describe_se(ConvParams p, int dtype, Launch* out) {
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_UNSUPPORTED, "squeeze-excitation: storage modes f32 and f16x2 only");
+  if (!p.in || !p.out || !p.wgt) return fail(UDP_ERR_ARG, "squeeze-excitation: null pointer");
+  const int V = dtype == UDP_F32 ? 4 : 8, Ch = p.up_shift[0];
+  if (p.Cin <= 0 || p.Cin % 32 || p.Cin > 512 || Ch < 1 || Ch > 256 || p.N <= 0) return fail(UDP_ERR_ARG, "squeeze-excitation: C %d, hidden %d", p.Cin, Ch);
+  out->fn = dtype == UDP_F32 ? reinterpret_cast<const void*>(&se_kernel<float>) : reinterpret_cast<const void*>(&se_kernel<H2>);
+  out->grid = dim3((unsigned)p.N);
+  out->block = dim3(256);
+  out->lds = (unsigned)((256 * V + 2 * p.Cin + 256 + Ch) * sizeof(float));
   out->p = p;
   return UDP_OK;
 }

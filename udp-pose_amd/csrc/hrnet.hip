@@ -56,11 +56,25 @@ struct udp_hrnet {
 
 static size_t esize(int dtype) { return dtype == UDP_BF16 ? 2 : 4; }   // bytes per stored element (F16X2: hi + lo)
 
+// udp_conv_op.relu as an activation code (udp_pose_hip.h, UDP_ACT_*).  Hard-swish exists as separate instantiations of
+// the stem kernels and of the plain 1x1 stride-1 NHWC convs only; everywhere else it is refused, never read as a ReLU.
+static int act_validate(const udp_conv_op& o, int dtype, bool has_res) {
+  if (o.relu < UDP_ACT_NONE || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "activation code %d (0 none, 1 ReLU, 2 hard-swish)", o.relu);
+  if (o.relu != UDP_ACT_HSWISH) return UDP_OK;
+  const bool plain1x1 = o.kind == UDP_OP_CONV && o.ks == 1 && o.stride == 1 && !o.group && !o.chain_cout && !o.n_up && !o.n_out2 && !has_res &&
+                        !o.in_stuff2 && o.out_buf != UDP_BUF_OUTPUT;
+  if (dtype == UDP_BF16 || (o.kind != UDP_OP_STEM && !plain1x1))
+    return fail(UDP_ERR_UNSUPPORTED, "hard-swish (activation code 2): UDP_OP_STEM and 1x1 stride-1 NHWC UDP_OP_CONV without addends, second outputs, "
+                "chain or group, in f32 / f16x2 only (kind %d, ks %d, stride %d)", o.kind, o.ks, o.stride);
+  return UDP_OK;
+}
+
 static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
   const int nb = (int)h->buf_elems.size();
   auto buf_ok = [&](int b, int64_t need) { return b >= 0 && b < nb && h->buf_elems[b] >= need; };
   const int64_t out_need = (int64_t)o.hout * o.wout * (o.out_pitch ? o.out_pitch : o.cout);
-  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_PIXSHUF) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_SE) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (const int rc = act_validate(o, h->dtype, o.res_buf != UDP_BUF_NONE)) return rc;
   if (o.lane < 0 || o.lane >= UDP_MAX_LANES || o.n_wait < 0 || o.n_wait > UDP_MAX_WAIT) return fail(UDP_ERR_ARG, "op %d: lane/n_wait", idx);
   for (int k = 0; k < o.n_wait; ++k)
     if (o.wait_op[k] < 0 || o.wait_op[k] >= idx) return fail(UDP_ERR_ARG, "op %d: wait_op %d must name an earlier op", idx, o.wait_op[k]);
@@ -98,8 +112,22 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
       return fail(UDP_ERR_ARG, "op %d: deconv weight / bias range outside the blob or misaligned", idx);
     return UDP_OK;
   }
+  if (o.kind == UDP_OP_SE) {
+    // squeeze-and-excitation (dwconv.hip); `out` may be the very view `in` is
+    const int rc = se_validate(o, h->dtype);
+    if (rc) return rc;
+    const int ipitch = o.in_pitch ? o.in_pitch : o.cin;
+    if (!buf_ok(o.in_buf, (int64_t)o.hin * o.win * ipitch) || !buf_ok(o.out_buf, out_need) || o.res_buf != UDP_BUF_NONE)
+      return fail(UDP_ERR_ARG, "op %d: squeeze-excitation buffers missing or too small (or a residual)", idx);
+    if (o.in_buf == o.out_buf && (o.in_coff != o.out_coff || ipitch != (o.out_pitch ? o.out_pitch : o.cout)))
+      return fail(UDP_ERR_ARG, "op %d: squeeze-excitation in place needs the same view for in and out", idx);
+    const size_t wbytes = ((size_t)2 * o.cin * o.chain_cout + o.chain_cout) * 4;
+    if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15))
+      return fail(UDP_ERR_ARG, "op %d: squeeze-excitation parameter block outside the blob or misaligned", idx);
+    return UDP_OK;
+  }
   if (o.kind == UDP_OP_DWCONV || o.kind == UDP_OP_PIXSHUF) {
-    // depthwise 3x3 conv + folded BatchNorm (+ the ShuffleV2 passthrough) / PixelShuffle(2) (dwconv.hip)
+    // depthwise conv + folded BatchNorm (+ the ShuffleV2 passthrough) / PixelShuffle(2) (dwconv.hip)
     const bool dw = o.kind == UDP_OP_DWCONV;
     const int rc = dw ? dwconv_validate(o, h->dtype) : pixshuf_validate(o, h->dtype);
     if (rc) return rc;
@@ -114,7 +142,7 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
     } else if (o.res_buf != UDP_BUF_NONE) {
       return fail(UDP_ERR_UNSUPPORTED, "op %d: %s takes no residual", idx, dw ? "depthwise conv" : "pixel shuffle");
     }
-    if (dw && (o.w_off < 0 || (size_t)o.w_off + (size_t)9 * o.cin * 4 > h->weights_bytes || (o.w_off & 15) || o.b_off < 0 ||
+    if (dw && (o.w_off < 0 || (size_t)o.w_off + (size_t)o.ks * o.ks * o.cin * 4 > h->weights_bytes || (o.w_off & 15) || o.b_off < 0 ||
                (size_t)o.b_off + (size_t)o.cin * 4 > h->weights_bytes || (o.b_off & 15)))
       return fail(UDP_ERR_ARG, "op %d: depthwise conv weight / bias range outside the blob or misaligned", idx);
     return UDP_OK;
@@ -276,7 +304,8 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
       h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;
     if (ops[i].kind == UDP_OP_BLOCK) h->flops += 2 * 2.0 * 9 * 32 * 32 * ops[i].hout * ops[i].wout;
     if (ops[i].kind == UDP_OP_DECONV) h->flops += 2.0 * 4 * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;   // 2x2 taps per output pixel
-    if (ops[i].kind == UDP_OP_DWCONV) h->flops += 2.0 * 9 * ops[i].cout * ops[i].hout * ops[i].wout;   // 9 MACs per output element
+    if (ops[i].kind == UDP_OP_DWCONV) h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cout * ops[i].hout * ops[i].wout;   // ks * ks MACs per output element
+    if (ops[i].kind == UDP_OP_SE) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // the two small products (pool and scale are not counted)
     if (ops[i].kind == UDP_OP_CONV && ops[i].chain_cout) h->flops += 2.0 * ops[i].cout * ops[i].chain_cout * ops[i].hout * ops[i].wout;
     h->ops.push_back(ops[i]);
   }
@@ -400,6 +429,10 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       p.up_shift[2] = o.chain_relu;
     }
     if (o.kind == UDP_OP_DWCONV) p.up_shift[0] = o.chain_cout;   // passthrough: real channels per half (n_up == 0)
+    if (o.kind == UDP_OP_SE) {
+      p.wgt = h->weights + o.w_off;
+      p.up_shift[0] = o.chain_cout;                              // hidden width
+    }
     if (o.kind == UDP_OP_BLOCK) {
       p.wgt = h->weights + o.w_off;
       p.bias = reinterpret_cast<const float*>(h->weights + o.b_off);
@@ -422,7 +455,8 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       case UDP_OP_MAXPOOL: rc = describe_maxpool(p, h->dtype, &ls[i]); break;
       case UDP_OP_BILINEAR: rc = describe_bilinear(p, h->dtype, &ls[i]); break;
       case UDP_OP_DECONV: rc = describe_deconv(p, h->dtype, &ls[i]); break;
-      case UDP_OP_DWCONV: rc = describe_dwconv(p, h->dtype, o.stride, &ls[i]); break;
+      case UDP_OP_DWCONV: rc = describe_dwconv(p, h->dtype, o.ks, o.stride, &ls[i]); break;
+      case UDP_OP_SE: rc = describe_se(p, h->dtype, &ls[i]); break;
       case UDP_OP_PIXSHUF: rc = describe_pixshuf(p, h->dtype, &ls[i]); break;
       default:
         if (o.chain_cout) {
@@ -758,9 +792,18 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (!o || !in || !out) return fail(UDP_ERR_ARG, "udp_conv2d_fused: null pointer");
   if (dtype != UDP_F32 && dtype != UDP_BF16 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "udp_conv2d_fused: dtype %d", dtype);
   if (n <= 0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: n=%d", n);
-  if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV && o->kind != UDP_OP_DWCONV && o->kind != UDP_OP_PIXSHUF)
+  if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV && o->kind != UDP_OP_DWCONV && o->kind != UDP_OP_PIXSHUF &&
+      o->kind != UDP_OP_SE)
     return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
-  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && (!weights || !bias)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (const int rc = act_validate(*o, dtype, res != nullptr)) return rc;
+  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && (!weights || (!bias && o->kind != UDP_OP_SE))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind == UDP_OP_SE) {
+    const int rc = se_validate(*o, dtype);
+    if (rc) return rc;
+    if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation takes no residual");
+    if (in == out && (o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
+      return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation in place needs the same view for in and out");
+  }
   if (o->kind == UDP_OP_DWCONV || o->kind == UDP_OP_PIXSHUF) {
     const bool dw = o->kind == UDP_OP_DWCONV;
     const int rc = dw ? dwconv_validate(*o, dtype) : pixshuf_validate(*o, dtype);
@@ -793,7 +836,9 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   p.Cout = o->cout;
   p.CoutPad = o->cout_pad;
   p.relu = o->relu;
-  if (o->kind == UDP_OP_DWCONV) {
+  if (o->kind == UDP_OP_SE) {
+    p.up_shift[0] = o->chain_cout;      // hidden width (se_validate: n_up == 0, n_out2 == 0)
+  } else if (o->kind == UDP_OP_DWCONV) {
     if (o->n_out2) {
       p.nout2 = 1;
       p.out2[0] = const_cast<void*>(up0);
@@ -844,7 +889,8 @@ static int conv2d_fused_impl(const udp_conv_op* o, int dtype, int n, const void*
   p.bn_ws = bn_ws;
   const int rc = o->kind == UDP_OP_FUSE     ? describe_fuse(p, dtype, &l)
                  : o->kind == UDP_OP_DECONV ? describe_deconv(p, dtype, &l)
-                 : o->kind == UDP_OP_DWCONV ? describe_dwconv(p, dtype, o->stride, &l)
+                 : o->kind == UDP_OP_DWCONV ? describe_dwconv(p, dtype, o->ks, o->stride, &l)
+                 : o->kind == UDP_OP_SE     ? describe_se(p, dtype, &l)
                  : o->kind == UDP_OP_PIXSHUF ? describe_pixshuf(p, dtype, &l)
                                             : describe_conv(p, dtype, o->ks, o->stride, &l);
   if (rc) return rc;
@@ -873,6 +919,7 @@ extern "C" int udp_conv2d_fused_group(udp_conv_item* items, int n_items, int dty
     const udp_conv_op* o = it.op;
     if (!o || o->kind != UDP_OP_CONV || o->n_up || o->out_buf == UDP_BUF_OUTPUT)
       return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused_group: member %d is not a plain NHWC conv", j);
+    if (o->relu == UDP_ACT_HSWISH) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused_group: member %d: hard-swish has no merged-launch form", j);
     if (it.bn_ws && (dtype == UDP_F16X2 || o->relu || it.res || (o->out_pitch && o->out_pitch != o->cout) || o->out_coff))
       return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused_group: member %d: BatchNorm sums need a plain fp32 / bf16 conv", j);
     ConvParams p;

@@ -428,5 +428,47 @@ def get_pose_net_shufflenetv2(cfg, is_train, **kwargs):
     return PoseShuffleNetV2Hip(cfg, **kwargs)
 
 
+class PoseShuffleNetV2PlusHip(PoseNetHip):
+    """pose_shufflenetv2_plus_pixel_shuffle (deep_hrnet/lib/models/pose_shufflenetv2_plus_pixel_shuffle.py:23-55: the
+    ShuffleNetV2+ Small / Medium / Large backbone -- 3x3 / 5x5 / 7x7 depthwise convs, hard-swish, squeeze-and-excitation
+    --, the pixel-shuffle (DUC) decoder, ``final_layer``) inference through the same C ABI; ``state_dict`` in the
+    reference module's key format (``LastSE`` / ``fc`` / ``classifier`` are accepted and unused, as in the reference's
+    forward).  Storage modes "f32" and "f16x2" (the depthwise and squeeze-excitation kernels have no bf16 form)."""
+
+    NAME = "pose_shufflenetv2_plus_pixel_shuffle"
+    DTYPES = ("f32", "f16x2")
+
+    def __init__(self, cfg, dtype="f32"):
+        from .shufflenet_plus_plan import shufflenet_plus_spec
+        if dtype not in self.DTYPES:
+            raise ValueError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
+        super().__init__(cfg, dtype)
+        self.extra = _get(cfg, "MODEL", "EXTRA")
+        self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
+        self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
+        self.spec = shufflenet_plus_spec(self.extra, self.num_joints, self.target_type)   # NotImplementedError for an unknown size ...
+
+    def param_shapes(self):
+        from .synth_shufflenet_plus import shufflenet_plus_param_shapes
+        sp = self.spec
+        return shufflenet_plus_param_shapes(model_size=sp["model_size"], num_joints=self.num_joints, target_type=self.target_type,
+                                            start_channels=sp["start_channels"], architecture=sp["architecture"],
+                                            final_kernel=sp["final_kernel"])
+
+    def init_weights(self, pretrained=""):
+        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+
+    def _make_program(self, h, w):
+        from .shufflenet_plus_plan import ShuffleNetV2PlusProgram
+        return ShuffleNetV2PlusProgram(self._sd, self.spec, h, w, self.dtype)
+
+
+def get_pose_net_shufflenetv2_plus(cfg, is_train, **kwargs):
+    """pose_shufflenetv2_plus_pixel_shuffle.py:58-67 (``get_pose_net``); inference only -- the weights come from
+    ``load_state_dict``."""
+    return PoseShuffleNetV2PlusHip(cfg, **kwargs)
+
+
 MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet,
-          "pose_shufflenetv2_10x_pixel_shuffle": get_pose_net_shufflenetv2}
+          "pose_shufflenetv2_10x_pixel_shuffle": get_pose_net_shufflenetv2,
+          "pose_shufflenetv2_plus_pixel_shuffle": get_pose_net_shufflenetv2_plus}

@@ -59,6 +59,8 @@ def _halves(r):
 
 
 class ShuffleNetV2Program(Program):
+    DW_KERNELS = (3,)
+
     def __init__(self, state_dict, spec, in_h, in_w, dtype="f32"):
         if dtype not in ("f32", "f16x2"):
             raise ValueError("pose_shufflenetv2_10x_pixel_shuffle: dtype %r; supported storage modes are 'f32' and 'f16x2' "
@@ -96,15 +98,16 @@ class ShuffleNetV2Program(Program):
         return out
 
     def _dw(self, conv, bn, x, cin, pos, stride, into=None, passthrough=None):
-        """Depthwise 3x3 conv + BatchNorm on the first ``cin`` stored channels of ``x``; ``pos[j]``: where logical
-        channel j of the [C,1,3,3] weight sits.  ``into = (tensor, coff)``; ``passthrough = (src, dst, r)``: the
+        """Depthwise k x k conv (k = 3, or 5 / 7 in the ShuffleNetV2+ planner) + BatchNorm on the first ``cin`` stored
+        channels of ``x``; ``pos[j]``: where logical channel j of the [C,1,k,k] weight sits.  ``into = (tensor, coff)``; ``passthrough = (src, dst, r)``: the
         x_proj copy of a stride-1 unit (include/udp_pose_hip.h, UDP_OP_DWCONV)."""
         w, b = self._fold(conv, bn)
-        if tuple(w.shape[1:]) != (1, 3, 3) or w.shape[0] != len(pos):
-            raise ValueError("%s.weight must be [%d,1,3,3]" % (conv, len(pos)))
+        ks = int(w.shape[2])
+        if tuple(w.shape[1:]) != (1, ks, ks) or ks not in self.DW_KERNELS or w.shape[0] != len(pos):
+            raise ValueError("%s.weight must be [%d,1,k,k], k one of %s" % (conv, len(pos), self.DW_KERNELS))
         idx = torch.tensor(pos)
-        wp = torch.zeros(9, cin, dtype=torch.float32)
-        wp[:, idx] = w.reshape(len(pos), 9).t()
+        wp = torch.zeros(ks * ks, cin, dtype=torch.float32)
+        wp[:, idx] = w.reshape(len(pos), ks * ks).t()
         bp = torch.zeros(cin, dtype=torch.float32)
         bp[idx] = b
         ho, wo = (x.h - 1) // stride + 1, (x.w - 1) // stride + 1
@@ -120,7 +123,7 @@ class ShuffleNetV2Program(Program):
             # ops_array() can zip it with ``out2`` and _reads() sees the dependency -- the kernel never reads add2;
             # ``chain_cout`` carries r, no chained conv
             views.update(res=src, res_coff=0, res_pitch=src.c, res_c=src.c, out2=[(dst, 0)], add2=[(src, 0)], chain_cout=r)
-        self._emit(_lib.UDP_OP_DWCONV, conv, x, out, ks=3, stride=stride, relu=0, cin=cin, cout=cin, cout_pad=cin, hout=ho, wout=wo,
+        self._emit(_lib.UDP_OP_DWCONV, conv, x, out, ks=ks, stride=stride, relu=0, cin=cin, cout=cin, cout_pad=cin, hout=ho, wout=wo,
                    w_off=self._put(wp.numpy().tobytes()), b_off=self._put(bp.numpy().tobytes()), **views)
         return out
 
@@ -199,5 +202,5 @@ class ShuffleNetV2Program(Program):
                 sd.used.add(k)              # BatchNorm bookkeeping / the ImageNet classifier forward() never applies (:160-165)
 
     def macs_per_image(self):
-        return super().macs_per_image() + sum(9 * op["cout"] * op["hout"] * op["wout"] for op in self._ops
+        return super().macs_per_image() + sum(op["ks"] ** 2 * op["cout"] * op["hout"] * op["wout"] for op in self._ops
                                               if op["kind"] == _lib.UDP_OP_DWCONV)
