@@ -97,8 +97,9 @@ enum udp_op_kind {
    * (UDP_F16X2, required there) the fragment-major blocks described at `wfmt` with tap = pt, scaled by 2^wexp
    * (udp_pose_amd.f16x2.pack_deconv_weights_ws builds it). */
   UDP_OP_DECONV = 11,
-  /* Depthwise Conv2d(C, C, ks, stride, ks / 2, groups=C, bias=False) + folded BatchNorm (+ ReLU if `relu` == 1;
-   * activation code 2 is refused): the dw convs of the ShuffleV2 units (deep_hrnet/lib/models/backbones/
+  /* Depthwise Conv2d(C, C, ks, stride, ks / 2, groups=C, bias=False) + folded BatchNorm (+ ReLU if `relu` == 1, SiLU
+   * if `relu` == 4 -- MobileViTv2, backbones/mobilevitv2.py:210-214, :898-908; activation code 2 is refused with
+   * UDP_ERR_UNSUPPORTED): the dw convs of the ShuffleV2 units (deep_hrnet/lib/models/backbones/
    * shufflenetv2.py:54-55, :66-67; the reference never puts a ReLU behind one, the field is honoured all the same) and
    * the 5x5 / 7x7 ones of ShuffleNetV2+ (backbones/shufflenetv2_plus.py:97, :119).  Per image, NHWC, UDP_F32 and
    * UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED).  ks = 3 | 5 | 7 (anything else: UDP_ERR_ARG), stride 1 | 2,
@@ -145,17 +146,61 @@ enum udp_op_kind {
    * NULL), fp32 in EVERY storage mode: W1 transposed [C][Ch], b1 [Ch], W2 transposed [Ch][C].  Pad channels carry
    * zero weights: m = 0.5 there and the stored zeros stay exact zeros.  All sums are fp32 in a fixed order that
    * depends on (C, Ch, HW) only, nothing is atomic: an image's result does not depend on the batch it arrives in. */
-  UDP_OP_SE = 14
+  UDP_OP_SE = 14,
+  /* nn.GroupNorm(1, C), eps 1e-5 -- what the reference calls "layer_norm_2d" (deep_hrnet/lib/models/backbones/
+   * mobilevitv2.py:139-140; the norms of LinearAttnFFN :783-794 and the closing one of MobileViTBlockv2 :1018-1022) --
+   * on an NHWC view of C stored channels, UDP_F32 and UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED); one launch, one
+   * workgroup per image.  The reference applies it to the unfolded [B, C, P, N] tensor; the statistics run over the
+   * whole sample, so on the NHWC map it is the same op (unfold / fold only re-index pixels).
+   *   mean = (1 / (r HW)) sum in[p][c]     var = (1 / (r HW)) sum (in[p][c] - mean)^2     (over the r real channels)
+   *   out[p][c] = fmaf((in[p][c] - mean) * rstd, gamma[c], beta[c]),  rstd = 1 / sqrt(var + 1e-5)      for c < r
+   *     (mean and the subtraction in fp64, the difference and rstd rounded to fp32, the rest in fp32)
+   *   out[p][c] = 0                                                                                     for r <= c < C
+   * cin == cout == cout_pad = C, a multiple of 32 up to 512; chain_cout = r, the real channels (1 <= r <= C; the first
+   * r of the view) -- the field carries a count here as it does for kinds 12 and 14, no chained conv; hout == hin,
+   * wout == win, any size >= 1.  in_coff / in_pitch / out_coff / out_pitch are honoured (multiples of 8).  relu must
+   * be 0; no addends, second outputs, group, wfmt.  `out` MAY be `in` (same buffer, same view -- the rule of kind 14):
+   * both statistics are complete before the first store and every element is read and written by one thread.
+   * Parameter block at w_off (udp_conv2d_fused: `weights`; `bias` may be NULL), fp32 in EVERY storage mode: gamma [C],
+   * beta [C], zeros at the pad channels.  The variance is two-pass (the mean first, then the squared deviations of a
+   * second read of the map): never E[x^2] - E[x]^2.  A thread accumulates in fp64 over its pixels in ascending order
+   * and the workgroup adds the per-thread sums in a fixed tree; the order depends on (C, r, HW) only, nothing is
+   * atomic: an image's result does not depend on the batch it arrives in.  Not counted in udp_hrnet_flops_per_image. */
+  UDP_OP_GNORM = 15,
+  /* The core of the separable ("linear") self-attention of MobileViTv2 for 2x2 patches: LinearSelfAttention.
+   * _forward_self_attn between qkv_proj and out_proj (backbones/mobilevitv2.py:671-689), with the F.unfold / F.fold
+   * around it (:1026-1055) folded into indexing: pixel (y, x) of the NHWC map is position p = 2 (y & 1) + (x & 1) of
+   * patch (y / 2, x / 2), and the soft-max over the patches runs separately for each of the four positions.
+   * UDP_F32 and UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED); one launch, one workgroup per image.  ks = 2 carries the
+   * patch size (anything else: UDP_ERR_ARG).  cout == cout_pad = C, a multiple of 32 up to 512; cin = 2C + 32: the
+   * output of the qkv conv as the planner stores it (through the conv's output-channel map) -- key at [0, C), value at
+   * [C, 2C), the query's single channel at 2C, zeros behind it.  hin == hout, win == wout, both even and hin * win <=
+   * 16384 (odd sizes: UDP_ERR_ARG; the reference resizes such maps bilinearly, :1095-1103).  Views are honoured
+   * (multiples of 8); `out` must not be `in`.  relu must be 0; no weights / bias (may be NULL), addends, second
+   * outputs, group, wfmt.  Per image and position class p:
+   *   m = max q over the class's pixels        s = exp(q - m) / sum exp(q - m)
+   *   ctx[p][c] = sum s k[.][c]                out[y][x][c] = max(v[y][x][c], 0) * ctx[p(y, x)][c]
+   * All fp32; UDP_F16X2 operands are decoded hi + lo * 2^-11 first and the result is split again on store, with the
+   * udp_f16x2_overflow range guard.  q is staged in LDS, so the map is read once (k, then v).  The class maximum and
+   * sum are reduced by one wave per class in a fixed butterfly; ctx is accumulated with fmaf by G pixel groups per
+   * class (class pixels g, g + G, ... in raster order) that are then added in the order g = 0 .. G-1; G depends on C
+   * only, nothing is atomic: an image's result does not depend on the batch it arrives in.  Pad channels have
+   * k = v = 0 and stay exact zeros.  udp_hrnet_flops_per_image counts 2 C HW (the weighted sum) for it. */
+  UDP_OP_LINATTN = 16
 };
 
 /* udp_conv_op.relu is an activation code.  UDP_ACT_HSWISH: v * (clamp(v + 3, 0, 6) / 6) in fp32, applied where the
  * ReLU is applied, before the value is stored -- in UDP_OP_STEM and in a 1x1 stride-1 UDP_OP_CONV writing NHWC
  * without addends (res / up), second outputs, a chain or a group, in UDP_F32 and UDP_F16X2 (wfmt 0 and 1, channel
- * views honoured).  Every other op and conv form answers it with UDP_ERR_UNSUPPORTED; a code outside 0..2 is
- * UDP_ERR_ARG. */
+ * views honoured).  Every other op and conv form answers it with UDP_ERR_UNSUPPORTED.
+ * UDP_ACT_SILU ("swish", nn.SiLU: the activation of every ConvLayer of MobileViTv2, backbones/mobilevitv2.py:78-79):
+ * v * (1 / (1 + expf(-v))) in fp32, in the same place -- honoured by the two forms above and by UDP_OP_DWCONV (every
+ * ks / stride it has); every other op and conv form answers it with UDP_ERR_UNSUPPORTED.  silu(0) = 0, so zero pad
+ * channels stay exact zeros.  Code 3 is not assigned and stays refused with UDP_ERR_ARG, as every code outside 0..4. */
 #define UDP_ACT_NONE 0
 #define UDP_ACT_RELU 1
 #define UDP_ACT_HSWISH 2
+#define UDP_ACT_SILU 4
 
 #define UDP_MAX_LANES 4
 #define UDP_MAX_WAIT 8
@@ -164,8 +209,8 @@ enum udp_op_kind {
 
 typedef struct udp_conv_op {
   int32_t kind;            /* enum udp_op_kind */
-  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7; pad = ks/2), stride 1|2 */
-  int32_t relu;            /* activation of the epilogue: UDP_ACT_NONE / UDP_ACT_RELU / UDP_ACT_HSWISH (see there) */
+  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7; pad = ks/2; UDP_OP_LINATTN: 2 = the patch size), stride 1|2 */
+  int32_t relu;            /* activation of the epilogue: UDP_ACT_NONE / UDP_ACT_RELU / UDP_ACT_HSWISH / UDP_ACT_SILU (see there) */
   int32_t cin, cout;       /* real channel counts (cin multiple of 16 for UDP_OP_CONV) */
   int32_t cout_pad;        /* cout rounded up to a multiple of 32: rows of `weights`/`bias` */
   int32_t hin, win, hout, wout;
@@ -257,8 +302,9 @@ double udp_hrnet_flops_per_image(const udp_hrnet* h);
 
 /* One fused conv launch on raw pointers (the operator the program above is made of; used by
  * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE,
- * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF or UDP_OP_SE: NHWC in / out, weights as documented there, no res / up -- except the
- * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`; UDP_OP_SE: `weights` = the parameter block, chain_cout = hidden width), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
+ * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM or UDP_OP_LINATTN: NHWC in / out, weights as documented there, no res / up -- except the
+ * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`; UDP_OP_SE / UDP_OP_GNORM: `weights` = the parameter block, chain_cout = hidden width / real channels;
+ * UDP_OP_LINATTN: no weights), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
  * its buffer ids and blob offsets are ignored except out_buf == UDP_BUF_OUTPUT, which selects
  * the NCHW fp32 output form.  in/res/ups/out: NHWC `dtype`; weights [ks*ks][cout_pad][cin]
  * `dtype`; bias fp32 [cout_pad].  Replaces conv+BN(+add)(+ReLU), pose_hrnet.py:43-59.

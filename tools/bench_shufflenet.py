@@ -4,11 +4,16 @@ per-op-class kernel time of udp_hrnet_profile (hipEvents around every launch, ea
 the achieved bytes/s on its algorithmic traffic (one read and one write of the map) next to the launch time of a
 UDP_OP_FUSE (an existing kernel that moves the same bytes) on a tensor of the same size, in the same session.
 
-    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32] [--model v2|plus]
+    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32] [--model v2|plus|mobilevitv2]
 
 ``--model plus``: pose_shufflenetv2_plus_pixel_shuffle (Small) instead, with the same measurements; its depthwise
 launches are classed by kernel size, and the squeeze-excitation launches and the 1x1 convs with the hard-swish
 epilogue get classes of their own.
+
+``--model mobilevitv2``: pose_mobilevitv2_pixel_shuffle (MODEL_SIZE 0.5) instead; group-norm, attention, the 1x1 convs
+with the SiLU epilogue and those with a residual get classes of their own, and a UDP_OP_GNORM and a UDP_OP_LINATTN
+launch on the layer-3 map (32 x 24, 64 channels; the attention reads the 160-channel qkv map) are timed against a
+UDP_OP_FUSE launch on the map they read.
 """
 import argparse
 import ctypes as C
@@ -33,6 +38,8 @@ NAME = "pose_shufflenetv2_10x_pixel_shuffle"
 EXTRA = {"START_CHANNELS": 256, "ARCHITECTURE": (512, 256, 128), "MODEL_SIZE": "1.0x", "FINAL_CONV_KERNEL": 1}
 PLUS_NAME = "pose_shufflenetv2_plus_pixel_shuffle"
 PLUS_EXTRA = dict(EXTRA, MODEL_SIZE="Small")
+MVIT_NAME = "pose_mobilevitv2_pixel_shuffle"
+MVIT_EXTRA = dict(EXTRA, MODEL_SIZE=0.5)
 
 
 def op_class(name, kind, ks, stride):
@@ -58,6 +65,17 @@ def op_class_plus(op):
         return "se"
     if op["kind"] == _lib.UDP_OP_CONV and op["relu"] == _lib.UDP_ACT_HSWISH:
         return "conv1x1_hs"
+    return op_class(op["name"], op["kind"], op["ks"], op["stride"])
+
+
+def op_class_mvit(op):
+    """Classes of the MobileViTv2 program: group norm, attention, depthwise by stride, and the 1x1 convs by epilogue."""
+    if op["kind"] == _lib.UDP_OP_GNORM:
+        return "gnorm"
+    if op["kind"] == _lib.UDP_OP_LINATTN:
+        return "linattn"
+    if op["kind"] == _lib.UDP_OP_CONV and op["ks"] == 1 and op["name"] != "final_layer":
+        return "conv1x1_silu" if op["relu"] == _lib.UDP_ACT_SILU else "conv1x1_res" if op["res"] is not None else "conv1x1"
     return op_class(op["name"], op["kind"], op["ks"], op["stride"])
 
 
@@ -114,10 +132,43 @@ def dw_vs_fuse(dtype, images, c=128, h=32, w=24):
             "fuse_gbytes_per_s": round(nbytes / ms_fu / 1e6, 1)}
 
 
-def run(dtype, n, steps, warmup, plus=False):
-    name = PLUS_NAME if plus else NAME
-    cfg = {"MODEL": {"NAME": name, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian", "EXTRA": PLUS_EXTRA if plus else EXTRA}}
-    if plus:
+def attn_vs_fuse(dtype, images, c=64, h=32, w=24):
+    """One UDP_OP_GNORM launch and one UDP_OP_LINATTN launch on the layer-3 map of the 0.5 net, each against a UDP_OP_FUSE
+    launch (out = relu(in)) on the map it reads: [h, w, c] for the norm, the [h, w, 2c + 32] qkv map for the attention."""
+    lib, dt = _lib.lib(), _lib.DTYPES[dtype]
+    cq = 2 * c + 32
+    a = torch.randn(images * h * w * cq, device="cuda").to(torch.float32)    # 4 bytes per element in both modes
+    if dtype == "f16x2":
+        a.view(torch.float16).fill_(0.5)
+    b = torch.empty_like(a)
+    block = torch.ones(2 * c, device="cuda")
+
+    def mk(kind, cin, cout, **kw):
+        o = _lib.ConvOp()
+        o.kind, o.ks, o.stride, o.cin, o.cout, o.cout_pad = kind, 1, 1, cin, cout, cout
+        o.hin, o.win, o.hout, o.wout = h, w, h, w
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+    gn, la = mk(_lib.UDP_OP_GNORM, c, c, chain_cout=c), mk(_lib.UDP_OP_LINATTN, cq, c, ks=2)
+    fu, fuq = mk(_lib.UDP_OP_FUSE, c, c, relu=1), mk(_lib.UDP_OP_FUSE, cq, cq, relu=1)
+    s = _lib.stream_ptr()
+    run = lambda o, wp: _lib.check(lib.udp_conv2d_fused(C.byref(o), dt, images, _lib.ptr(a), wp, None, None, None, None, None, _lib.ptr(b), s))
+    t = _samples([lambda: run(gn, _lib.ptr(block)), lambda: run(fu, None), lambda: run(la, None), lambda: run(fuq, None)], reps=300)
+    us = lambda k: round(t[k][0] * 1e3, 2)
+    return {"shape": [images, h, w, c], "qkv_channels": cq, "windows": "7 alternating windows of 300 launches each",
+            "gnorm_us": us(0), "fuse_us": us(1), "gnorm_over_fuse": round(t[0][0] / t[1][0], 3),
+            "linattn_us": us(2), "fuse_qkv_us": us(3), "linattn_over_fuse_qkv": round(t[2][0] / t[3][0], 3),
+            "us_min_max": [[round(lo * 1e3, 2), round(hi * 1e3, 2)] for _, lo, hi in t]}
+
+
+def run(dtype, n, steps, warmup, plus=False, mvit=False):
+    name = MVIT_NAME if mvit else PLUS_NAME if plus else NAME
+    cfg = {"MODEL": {"NAME": name, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian", "EXTRA": MVIT_EXTRA if mvit else PLUS_EXTRA if plus else EXTRA}}
+    if mvit:
+        from udp_pose_amd.synth_mobilevitv2 import synth_mobilevitv2_state_dict
+        sd = synth_mobilevitv2_state_dict(seed=7)
+    elif plus:
         from udp_pose_amd.synth_shufflenet_plus import synth_shufflenet_plus_state_dict
         sd = synth_shufflenet_plus_state_dict(seed=7)
     else:
@@ -139,18 +190,20 @@ def run(dtype, n, steps, warmup, plus=False):
     ms_op, desc = net.profile(x, flip_test=True)           # second run: warm caches, kernels loaded
     classes = {}
     for k, ((name, kind, ks, stride, cin, cout, hout, wout), t) in enumerate(zip(desc, ms_op)):
-        e = classes.setdefault(op_class_plus(prog._ops[k]) if plus else op_class(name, kind, ks, stride), {"launches": 0, "ms": 0.0})
+        cls = op_class_mvit(prog._ops[k]) if mvit else op_class_plus(prog._ops[k]) if plus else op_class(name, kind, ks, stride)
+        e = classes.setdefault(cls, {"launches": 0, "ms": 0.0})
         e["launches"] += 1
         e["ms"] += float(t)
     total = sum(e["ms"] for e in classes.values())
     for e in classes.values():
         e["share"] = round(e["ms"] / total, 4)
         e["ms"] = round(e["ms"], 4)
+    side = {"attn_vs_fuse": attn_vs_fuse(dtype, 2 * n)} if mvit else {"dwconv_vs_fuse": dw_vs_fuse(dtype, 2 * n)}
     return {"dtype": dtype, "images_per_s": round(n / ms * 1000.0, 1), "ms_per_step": round(ms, 3),
             "ms_per_step_min_max": [round(ms_lo, 3), round(ms_hi, 3)], "windows": "5 windows of %d steps, median" % steps,
             "launches_per_forward": int(lib.udp_hrnet_num_launches(handle)),
             "gflop_per_image": round(lib.udp_hrnet_flops_per_image(handle) / 1e9, 3),
-            "kernel_ms_profiled": round(total, 3), "by_class": classes, "dwconv_vs_fuse": dw_vs_fuse(dtype, 2 * n)}
+            "kernel_ms_profiled": round(total, 3), "by_class": classes, **side}
 
 
 def main():
@@ -159,11 +212,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--dtypes", default="f16x2,f32")
-    ap.add_argument("--model", choices=("v2", "plus"), default="v2")
+    ap.add_argument("--model", choices=("v2", "plus", "mobilevitv2"), default="v2")
     a = ap.parse_args()
-    plus = a.model == "plus"
-    res = [run(d, a.batch, a.steps, a.warmup, plus) for d in a.dtypes.split(",")]
-    workload = "pose_shufflenetv2_plus_pixel_shuffle Small" if plus else "pose_shufflenetv2_10x_pixel_shuffle 1.0x"
+    plus, mvit = a.model == "plus", a.model == "mobilevitv2"
+    res = [run(d, a.batch, a.steps, a.warmup, plus, mvit) for d in a.dtypes.split(",")]
+    workload = ("pose_mobilevitv2_pixel_shuffle 0.5" if mvit else "pose_shufflenetv2_plus_pixel_shuffle Small" if plus
+                else "pose_shufflenetv2_10x_pixel_shuffle 1.0x")
     out = {"workload": workload + " 256x192 flip-test + DARK decode", "batch": a.batch, "results": res}
     if len(res) == 2:
         out["f16x2_over_f32"] = round(res[0]["images_per_s"] / res[1]["images_per_s"], 3)

@@ -76,7 +76,7 @@ struct ConvParams {
   unsigned mTX, mTY;     // ceil(2^32/d), 0 for d == 1 (tile index decode, t < 65536)
   int ntiles;            // all tiles of the launch (persistent workgroups stride over them)
   unsigned mIW, mIH, mRT, mTW;  // ceil(2^20/d): x/d == (x*m) >> 20 for x*d < 2^20 (24-bit multiply)
-  int relu;              // udp_conv_op.relu: 0 none, 1 ReLU, 2 hard-swish (the *_hs instantiations only)
+  int relu;              // udp_conv_op.relu: 0 none, 1 ReLU, 2 hard-swish / 4 SiLU (the *_hs / SILU instantiations only)
   int out_nchw_f32;      // epilogue writes NCHW fp32 (network output) instead of NHWC T
   int flip_from;         // stem only: images >= flip_from read image (n - flip_from) mirrored in x
   int sbuf;              // conv_mfma_kernel: one stage buffer instead of two (set by conv_choose_tile)
@@ -143,6 +143,12 @@ int describe_pixshuf(ConvParams p, int dtype, Launch* out);
 int se_validate(const udp_conv_op& o, int dtype);                // UDP_OP_SE (squeeze-and-excitation, one workgroup per image)
 int describe_se(ConvParams p, int dtype, Launch* out);
 int dwconv_h2_overflow(hipStream_t s, int reset, int* flag);
+// attn.hip: GroupNorm(1, C) (UDP_OP_GNORM) and the separable self-attention core (UDP_OP_LINATTN), one workgroup per image
+int gnorm_validate(const udp_conv_op& o, int dtype);
+int linattn_validate(const udp_conv_op& o, int dtype);
+int describe_gnorm(ConvParams p, int dtype, Launch* out);
+int describe_linattn(ConvParams p, int dtype, Launch* out);
+int attn_h2_overflow(hipStream_t s, int reset, int* flag);
 int conv_h2_overflow(hipStream_t s, int reset, int* flag);       // conv.hip / conv_ws.hip / psa.hip: their g_h2_overflow
 int conv_ws_h2_overflow(hipStream_t s, int reset, int* flag);
 int psa_h2_overflow(hipStream_t s, int reset, int* flag);

@@ -116,9 +116,9 @@ __device__ __forceinline__ void mfma_chunk_h2(f32x4 (&acc)[MBW][NB], f32x4 (&acc
 }
 
 // MBW = 16-pixel blocks per wave (ceil(M/64)); NCHW = epilogue writes the fp32 NCHW network output.
-// HS: the hard-swish instantiations (udp_conv_op.relu == UDP_ACT_HSWISH; conv1x1_hs_kernel below) -- the epilogue
-// applies v * (clamp(v + 3, 0, 6) / 6) where the others apply the ReLU.
-template <typename T, int KS, int STRIDE, int NB, int MBW, bool NCHW, int NW, bool HS = false>
+// HS: the hard-swish / SiLU instantiations (HS = udp_conv_op.relu = UDP_ACT_HSWISH | UDP_ACT_SILU; conv1x1_hs_kernel
+// below) -- the epilogue applies act_hs<HS> where the others apply the ReLU.
+template <typename T, int KS, int STRIDE, int NB, int MBW, bool NCHW, int NW, int HS = 0>
 __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, const int tile_id, const int cb) {
   constexpr int CK = Tr<T>::CK;
   constexpr int ESZ = Tr<T>::ESZ;
@@ -348,7 +348,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, const int ti
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) v[nb][q] = hswish(v[nb][q]);
+          for (int q = 0; q < 4; ++q) v[nb][q] = act_hs<HS>(v[nb][q]);
       } else
       if (p.relu) {
 #pragma unroll
@@ -418,11 +418,11 @@ __global__ __launch_bounds__(NW * 64) void conv_mfma_kernel(const ConvParams p) 
   conv_mfma_body<T, KS, STRIDE, NB, MBW, NCHW, NW>(p, blockIdx.x, blockIdx.y);
 }
 
-// 1x1 stride-1 NHWC conv + hard-swish: the same body with the HS epilogue (4 waves; describe_conv picks it for
-// udp_conv_op.relu == UDP_ACT_HSWISH, which hrnet.hip admits for exactly this form)
-template <typename T, int NB, int MBW>
+// 1x1 stride-1 NHWC conv + hard-swish / SiLU: the same body with the HS epilogue (4 waves; describe_conv picks it for
+// udp_conv_op.relu == UDP_ACT_HSWISH | UDP_ACT_SILU, which hrnet.hip admits for exactly this form)
+template <typename T, int NB, int MBW, int ACT>
 __global__ __launch_bounds__(256) void conv1x1_hs_kernel(const ConvParams p) {
-  conv_mfma_body<T, 1, 1, NB, MBW, false, 4, true>(p, blockIdx.x, blockIdx.y);
+  conv_mfma_body<T, 1, 1, NB, MBW, false, 4, ACT>(p, blockIdx.x, blockIdx.y);
 }
 
 // Horizontal fusion: up to 4 independent convs (the same-depth convs of different HRNet branches, which
@@ -825,7 +825,7 @@ __global__ __launch_bounds__(NW * 64) void basic_block_c32_kernel(const ConvPara
 // VALU form (27 taps), + folded BN + ReLU, NHWC output.  pose_hrnet.py:290-292,
 // :437-439.  Images n >= flip_from read image n - flip_from mirrored along W
 // (flip-test second pass, function.py:154-156).
-template <typename T, bool HS = false>      // HS: + hard-swish instead of the ReLU (UDP_ACT_HSWISH)
+template <typename T, int HS = 0>      // HS: + hard-swish / SiLU instead of the ReLU (the activation code)
 __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const ConvParams p) {
   __shared__ __attribute__((aligned(16))) float w_s[27 * 64];
   __shared__ __attribute__((aligned(16))) float b_s[64];
@@ -874,7 +874,7 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const ConvParams p) {
     f32x4 v = {acc[q], acc[q + 1], acc[q + 2], acc[q + 3]};
     if constexpr (HS) {
 #pragma unroll
-      for (int z = 0; z < 4; ++z) v[z] = hswish(v[z]);
+      for (int z = 0; z < 4; ++z) v[z] = act_hs<HS>(v[z]);
     } else
     if (p.relu) {
 #pragma unroll
@@ -969,7 +969,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const ConvParams p) {
 // per workgroup in LDS from the fp32 [ky][kx][ci][64] weights; a lane gathers the 8 K values of its pixel straight
 // from the input (neighbouring pixels share cache lines) and splits each into hi + lo (bf16: the input keeps ~16
 // bits through two MFMAs on bf16 weights; H2: three fp16 MFMAs on hi/lo weights, as everywhere in that mode).
-template <typename T, int KS, bool HS = false>      // HS: + hard-swish instead of the ReLU (UDP_ACT_HSWISH)
+template <typename T, int KS, int HS = 0>      // HS: + hard-swish / SiLU instead of the ReLU (the activation code)
 __global__ __launch_bounds__(256) void stem_mfma_k(const ConvParams p) {
   constexpr bool SPLIT = std::is_same<T, H2>::value;
   constexpr int K = KS * KS * 3, NS = (K + 31) / 32, PAD = KS / 2, WPL = SPLIT ? 2 : 1;
@@ -1064,7 +1064,7 @@ __global__ __launch_bounds__(256) void stem_mfma_k(const ConvParams p) {
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[nb][q] = hswish(acc[nb][q]);
+        for (int q = 0; q < 4; ++q) acc[nb][q] = act_hs<HS>(acc[nb][q]);
     } else
     if (p.relu) {
 #pragma unroll
@@ -1335,11 +1335,11 @@ static int describe_one(const ConvParams& p, size_t lds, Launch* out) {
   return UDP_OK;
 }
 
-// hard-swish form of the 1x1 stride-1 NHWC conv (conv1x1_hs_kernel)
-template <typename T, int NB, int MBW>
+// hard-swish / SiLU form of the 1x1 stride-1 NHWC conv (conv1x1_hs_kernel)
+template <typename T, int NB, int MBW, int ACT>
 static int describe_hs_one(const ConvParams& p, size_t lds, Launch* out) {
   static bool attr_set = false;
-  const void* kern = reinterpret_cast<const void*>(&conv1x1_hs_kernel<T, NB, MBW>);
+  const void* kern = reinterpret_cast<const void*>(&conv1x1_hs_kernel<T, NB, MBW, ACT>);
   if (!attr_set) {
     UDP_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
@@ -1354,10 +1354,10 @@ static int describe_hs_one(const ConvParams& p, size_t lds, Launch* out) {
 template <typename T>
 static int describe_hs(const ConvParams& p, int nb, int mbw, size_t lds, Launch* out) {
 #define UDP_HS(B, M) \
-  if (nb == B && mbw == M) return describe_hs_one<T, B, M>(p, lds, out);
+  if (nb == B && mbw == M) return p.relu == UDP_ACT_SILU ? describe_hs_one<T, B, M, UDP_ACT_SILU>(p, lds, out) : describe_hs_one<T, B, M, UDP_ACT_HSWISH>(p, lds, out);
   UDP_HS(2, 1) UDP_HS(2, 2) UDP_HS(2, 3) UDP_HS(2, 4) UDP_HS(4, 1) UDP_HS(4, 2) UDP_HS(4, 3) UDP_HS(4, 4)
 #undef UDP_HS
-  return fail(UDP_ERR_UNSUPPORTED, "1x1 conv + hard-swish: no kernel for nb=%d, %d pixel blocks per wave", nb, mbw);
+  return fail(UDP_ERR_UNSUPPORTED, "1x1 conv + hard-swish / SiLU: no kernel for nb=%d, %d pixel blocks per wave", nb, mbw);
 }
 
 template <typename T, int KS, int STRIDE, int NB, bool NCHW>
@@ -1511,8 +1511,8 @@ int describe_conv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
     return fail(UDP_ERR_UNSUPPORTED, "conv tensor exceeds the 2 GiB the 32-bit buffer offsets cover; split the batch");
   if (p.in_stuff2 && (dtype == UDP_F16X2 || stride != 1 || (p.Hin & 1) || (p.Win & 1)))
     return fail(UDP_ERR_UNSUPPORTED, "in_stuff2: a stride-1 fp32 / bf16 conv over an even-sized stuffed image");
-  if (p.relu == UDP_ACT_HSWISH && (ks != 1 || stride != 1 || p.out_nchw_f32 || p.res || p.nup || p.nout2 || p.in_stuff2 || p.bn_ws || dtype == UDP_BF16))
-    return fail(UDP_ERR_UNSUPPORTED, "hard-swish (activation code 2): plain 1x1 stride-1 NHWC convs in f32 / f16x2 only");
+  if (p.relu >= UDP_ACT_HSWISH && (ks != 1 || stride != 1 || p.out_nchw_f32 || p.res || p.nup || p.nout2 || p.in_stuff2 || p.bn_ws || dtype == UDP_BF16))
+    return fail(UDP_ERR_UNSUPPORTED, "hard-swish / SiLU (activation codes 2, 4): plain 1x1 stride-1 NHWC convs in f32 / f16x2 only");
   if (p.nout2 && p.wfmt != 1) return fail(UDP_ERR_UNSUPPORTED, "second outputs need the weight-stationary split-fp16 conv (wfmt 1)");
   if (p.wfmt == 1) {
     if (dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "wfmt 1 (fragment-major weights) needs UDP_F16X2");
@@ -1527,7 +1527,7 @@ int describe_conv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
   if (getenv("UDP_POSE_DEBUG_TILES"))
     fprintf(stderr, "conv k%d s%d %dx%d C%d->%d: G=%d R=%d TW=%d NB=%d mbw=%d lds=%zu wgs=%d\n", ks, stride, p.Hout, p.Wout, p.Cin,
             p.Cout, p.G, p.R, p.TW, nb, mbw, lds, p.ntiles * (p.CoutPad / (nb * 16)));
-  if (p.relu == UDP_ACT_HSWISH) return dtype == UDP_F32 ? describe_hs<float>(p, nb, mbw, lds, out) : describe_hs<H2>(p, nb, mbw, lds, out);
+  if (p.relu >= UDP_ACT_HSWISH) return dtype == UDP_F32 ? describe_hs<float>(p, nb, mbw, lds, out) : describe_hs<H2>(p, nb, mbw, lds, out);
   if (dtype == UDP_BF16 && getenv("UDP_POSE_NO_PERSIST") == nullptr) {
     const int rc = describe_persist(p, ks, stride, nb, mbw, out);
     if (rc <= 0) return rc;
@@ -1541,7 +1541,7 @@ int describe_conv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
 // into a conv_mfma_multi node): every member uses the instantiation <bf16, 3, 1, NB=2, MBW=4, 4 waves>.
 // Returns 1 when the conv does not qualify (the caller falls back to describe_conv).
 int describe_conv_grouped(ConvParams p, int dtype, int ks, int stride, Launch* out) {
-  if (p.relu == UDP_ACT_HSWISH) return fail(UDP_ERR_UNSUPPORTED, "hard-swish (activation code 2) has no merged-launch form");
+  if (p.relu >= UDP_ACT_HSWISH) return fail(UDP_ERR_UNSUPPORTED, "hard-swish / SiLU (activation codes 2, 4) have no merged-launch form");
   if (p.wfmt == 1 && dtype == UDP_F16X2 && stride == 1 && (ks == 1 || ks == 3) && !p.out_nchw_f32 && !p.nup) {
     // member of a conv_ws_multi launch when its tile comes out with 6 pixel blocks per wave (groupable != 0),
     // a launch of its own otherwise
@@ -1627,18 +1627,20 @@ int describe_multi(const Launch* members, int n, ConvMulti* m, Launch* out) {
 int describe_stem(const ConvParams& p, int dtype, Launch* out) {
   if (p.Cout != 64) return fail(UDP_ERR_UNSUPPORTED, "stem conv expects 64 output channels, got %d", p.Cout);
   const long total = (long)p.N * p.Hout * p.Wout;
-  if (p.relu == UDP_ACT_HSWISH) {       // the hard-swish instantiations
-    if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "stem conv + hard-swish: storage modes f32 and f16x2 only");
+  if (p.relu >= UDP_ACT_HSWISH) {       // the hard-swish / SiLU instantiations
+    const bool si = p.relu == UDP_ACT_SILU;
+    if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "stem conv + hard-swish / SiLU: storage modes f32 and f16x2 only");
     out->block = dim3(256);
     out->p = p;
     if (dtype == UDP_F16X2 && getenv("UDP_POSE_STEM_VALU") == nullptr) {
       const long ntile = (total + 15) / 16;
-      out->fn = reinterpret_cast<const void*>(&stem_mfma_k<H2, 3, true>);
+      out->fn = si ? reinterpret_cast<const void*>(&stem_mfma_k<H2, 3, UDP_ACT_SILU>) : reinterpret_cast<const void*>(&stem_mfma_k<H2, 3, UDP_ACT_HSWISH>);
       out->grid = dim3((unsigned)((ntile + 3) / 4 < 2048 ? (ntile + 3) / 4 : 2048));
       out->lds = 1 * 4 * 2 * 1024;
       return UDP_OK;
     }
-    out->fn = dtype == UDP_F32 ? reinterpret_cast<const void*>(&stem_conv_kernel<float, true>) : reinterpret_cast<const void*>(&stem_conv_kernel<H2, true>);
+    out->fn = dtype == UDP_F32 ? (si ? reinterpret_cast<const void*>(&stem_conv_kernel<float, UDP_ACT_SILU>) : reinterpret_cast<const void*>(&stem_conv_kernel<float, UDP_ACT_HSWISH>))
+                               : (si ? reinterpret_cast<const void*>(&stem_conv_kernel<H2, UDP_ACT_SILU>) : reinterpret_cast<const void*>(&stem_conv_kernel<H2, UDP_ACT_HSWISH>));
     out->grid = dim3((unsigned)((total + 63) / 64));
     out->lds = 0;
     return UDP_OK;

@@ -44,6 +44,14 @@ constexpr float kLoScale = 2048.f, kLoInv = 1.f / 2048.f;
 
 // hard-swish (udp_pose_hip.h, UDP_ACT_HSWISH), fp32: v * (clamp(v + 3, 0, 6) / 6)
 __device__ __forceinline__ float hswish(float v) { return v * (__builtin_fminf(__builtin_fmaxf(v + 3.f, 0.f), 6.f) / 6.f); }
+// SiLU / "swish" (udp_pose_hip.h, UDP_ACT_SILU), fp32: v * (1 / (1 + expf(-v))); silu(0) = 0
+__device__ __forceinline__ float silu(float v) { return v * (1.f / (1.f + expf(-v))); }
+// the activation of an HS instantiation; HS = its activation code (UDP_ACT_HSWISH or UDP_ACT_SILU)
+template <int HS>
+__device__ __forceinline__ float act_hs(float v) {
+  if constexpr (HS == UDP_ACT_SILU) return silu(v);
+  else return hswish(v);
+}
 
 constexpr int ROWB = 64;   // LDS row: one pixel's (or one weight row's) 64-byte channel chunk
 constexpr int MAXG = 10;   // 16-row staging groups per wave for the input tile (<= 640 rows)

@@ -37,8 +37,8 @@ __device__ __forceinline__ void add_res_h2(f32x4 (&v)[NB], const ResH2<NB>& o) {
   for (int h = 0; h < NB / 2; ++h) h2_add8(v[2 * h], v[2 * h + 1], __builtin_bit_cast(f16x8, o.hi[h]), __builtin_bit_cast(f16x8, o.lo[h]));
 }
 
-// HS: the hard-swish instantiations (udp_conv_op.relu == UDP_ACT_HSWISH; conv_ws_hs_kernel below)
-template <int KS, int STRIDE, int PB, int CP, bool NCHW, bool OUT2 = false, bool HS = false>
+// HS: the hard-swish / SiLU instantiations (HS = udp_conv_op.relu = UDP_ACT_HSWISH | UDP_ACT_SILU; conv_ws_hs_kernel below)
+template <int KS, int STRIDE, int PB, int CP, bool NCHW, bool OUT2 = false, int HS = 0>
 __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile_id, const int cby) {
   using T = H2;
   constexpr int CK = 32, ESZ = 2, NB = 2, NW = 4;
@@ -365,7 +365,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) v[nb][q] = hswish(v[nb][q]);
+          for (int q = 0; q < 4; ++q) v[nb][q] = act_hs<HS>(v[nb][q]);
       } else
       if (p.relu) {
 #pragma unroll
@@ -446,12 +446,12 @@ __global__ __launch_bounds__(256, 2) void conv_ws_h2_kernel(const ConvParams p) 
   conv_ws_body<KS, STRIDE, PB, CP, NCHW, KS == 3 && STRIDE == 1 && !NCHW>(p, tile, cby);
 }
 
-// 1x1 stride-1 NHWC conv + hard-swish (udp_conv_op.relu == UDP_ACT_HSWISH): the same body with the HS epilogue
-template <int PB, int CP>
+// 1x1 stride-1 NHWC conv + hard-swish / SiLU (udp_conv_op.relu == ACT): the same body with the HS epilogue
+template <int PB, int CP, int ACT>
 __global__ __launch_bounds__(256, 2) void conv_ws_hs_kernel(const ConvParams p) {
   int tile, cby;
   ws_decode(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x, gridDim.y, tile, cby);
-  conv_ws_body<1, 1, PB, CP, false, false, true>(p, tile, cby);
+  conv_ws_body<1, 1, PB, CP, false, false, ACT>(p, tile, cby);
 }
 
 // Merged launch of up to 4 independent weight-stationary convs (same-depth convs of different HRNet branches):
@@ -518,10 +518,10 @@ static int describe_ws_pb(const ConvParams& p, int pb, int cp, size_t lds, Launc
 #undef UDP_WS
   return 1;
 }
-template <int PB, int CP>
+template <int PB, int CP, int ACT>
 static int describe_ws_hs_one(const ConvParams& p, size_t lds, Launch* out) {
   static bool attr_set = false;
-  const void* kern = reinterpret_cast<const void*>(&conv_ws_hs_kernel<PB, CP>);
+  const void* kern = reinterpret_cast<const void*>(&conv_ws_hs_kernel<PB, CP, ACT>);
   if (!attr_set) {
     UDP_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
@@ -535,7 +535,7 @@ static int describe_ws_hs_one(const ConvParams& p, size_t lds, Launch* out) {
 }
 static int describe_ws_hs(const ConvParams& p, int pb, int cp, size_t lds, Launch* out) {
 #define UDP_WS(B, C) \
-  if (pb == B && cp == C) return describe_ws_hs_one<B, C>(p, lds, out);
+  if (pb == B && cp == C) return p.relu == UDP_ACT_SILU ? describe_ws_hs_one<B, C, UDP_ACT_SILU>(p, lds, out) : describe_ws_hs_one<B, C, UDP_ACT_HSWISH>(p, lds, out);
   UDP_WS(2, 1) UDP_WS(3, 1) UDP_WS(4, 1) UDP_WS(6, 1) UDP_WS(2, 2) UDP_WS(3, 2) UDP_WS(4, 2) UDP_WS(6, 2)
   UDP_WS(2, 4) UDP_WS(3, 4) UDP_WS(4, 4) UDP_WS(6, 4)
 #undef UDP_WS
@@ -613,8 +613,8 @@ static long g_ws_fill_wgs = 512;
 void ws_set_fill_wgs(long wgs) { g_ws_fill_wgs = wgs; }
 
 int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped) {
-  if (p.relu == UDP_ACT_HSWISH && (ks != 1 || stride != 1 || p.out_nchw_f32 || p.res || p.nup || p.nout2 || grouped))
-    return fail(UDP_ERR_UNSUPPORTED, "hard-swish (activation code 2): plain 1x1 stride-1 NHWC convs on their own launch only");
+  if (p.relu >= UDP_ACT_HSWISH && (ks != 1 || stride != 1 || p.out_nchw_f32 || p.res || p.nup || p.nout2 || grouped))
+    return fail(UDP_ERR_UNSUPPORTED, "hard-swish / SiLU (activation codes 2, 4): plain 1x1 stride-1 NHWC convs on their own launch only");
   if ((stride != 1 && stride != 2) || (ks != 3 && ks != 1) || (p.out_nchw_f32 && stride != 1))
     return fail(UDP_ERR_UNSUPPORTED, "fragment-major weights (wfmt 1): conv ks=%d stride=%d nchw_out=%d has no weight-stationary kernel",
                 ks, stride, p.out_nchw_f32);
@@ -667,7 +667,7 @@ int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped
   if (ks == 3 && stride == 1 && p.out_nchw_f32) rc = describe_ws_pb<3, 1, true>(p, best.pb, best.cp, best.lds, out);   // the net's NCHW fp32 output (RSN head)
   if (ks == 3 && stride == 2) rc = describe_ws_pb<3, 2, false>(p, best.pb, best.cp, best.lds, out);
   if (ks == 1 && stride == 1 && !p.out_nchw_f32)
-    rc = p.relu == UDP_ACT_HSWISH ? describe_ws_hs(p, best.pb, best.cp, best.lds, out) : describe_ws_pb<1, 1, false>(p, best.pb, best.cp, best.lds, out);
+    rc = p.relu >= UDP_ACT_HSWISH ? describe_ws_hs(p, best.pb, best.cp, best.lds, out) : describe_ws_pb<1, 1, false>(p, best.pb, best.cp, best.lds, out);
   if (ks == 1 && stride == 1 && p.out_nchw_f32) rc = describe_ws_pb<1, 1, true>(p, best.pb, best.cp, best.lds, out);   // (HRNet final_layer)
   if (ks == 1 && stride == 2) rc = describe_ws_pb<1, 2, false>(p, best.pb, best.cp, best.lds, out);
   if (rc == 1) return fail(UDP_ERR_UNSUPPORTED, "weight-stationary conv: no kernel for PB=%d CP=%d", best.pb, best.cp);

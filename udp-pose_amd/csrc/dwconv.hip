@@ -22,58 +22,9 @@
 // The shuffle passthrough of a stride-1 ShuffleV2 unit (shufflenetv2.py:77-92) rides in the same launch: the thread
 // that stores output pixel (n, y, x), channels c..c+V-1 also copies the V selected channels of the unit's input to
 // the unit's output (udp_pose_hip.h, UDP_OP_DWCONV).  A selection: bit patterns are moved, never decoded.
-#include "conv_dev.h"
+#include "dw_dev.h"
 
 namespace udp {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T>
-struct DwTr;
-template <>
-struct DwTr<float> {
-  static constexpr int V = 4, PL = 1;
-  using E = uint32_t;      // one stored unit of a plane
-  using Vec = u32x4;       // 16 bytes of them
-};
-template <>
-struct DwTr<H2> {
-  static constexpr int V = 8, PL = 2;
-  using E = uint16_t;
-  using Vec = u16x8;
-};
-
-// V consecutive channels from `c` of pixel `pix` of the input view, decoded to fp32
-template <typename T, int V>
-__device__ __forceinline__ void dw_load(const ConvParams& p, size_t pix, int c, float (&x)[V]) {
-  if constexpr (std::is_same<T, float>::value) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.in) + pix * (size_t)p.in_pitch + p.in_coff + c);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = v[k];
-  } else {
-    const _Float16* q = reinterpret_cast<const _Float16*>(p.in) + pix * (2 * (size_t)p.in_pitch) + p.in_coff + c;
-    const f16x8 hi = *reinterpret_cast<const f16x8*>(q), lo = *reinterpret_cast<const f16x8*>(q + p.in_pitch);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = (float)hi[k] + (float)lo[k] * kLoInv;    // lo * 2^-11 is exact
-  }
-}
-
-template <typename T, int V>
-__device__ __forceinline__ void dw_store(const ConvParams& p, size_t pix, int c, const float (&a)[V]) {
-  float v[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) v[k] = p.relu ? __builtin_fmaxf(a[k], 0.f) : a[k];
-  if constexpr (std::is_same<T, float>::value) {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + pix * (size_t)p.out_pitch + p.out_coff + c) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-    f16x8 hi, lo;
-    h2_split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, hi, lo);     // raises the range flag
-    _Float16* q = reinterpret_cast<_Float16*>(p.out) + pix * (2 * (size_t)p.out_pitch) + p.out_coff + c;
-    *reinterpret_cast<f16x8*>(q) = hi;
-    *reinterpret_cast<f16x8*>(q + p.out_pitch) = lo;
-  }
-}
 
 // the three taps of kernel row KY on one input row; v0 / v2: the left / right column lies inside the image
 template <int KY, int V>
@@ -124,7 +75,7 @@ __device__ __forceinline__ void dw_passthrough(const ConvParams& p, size_t pix, 
 
 // thread = (image, row strip, output column, channel group); p.R output rows per strip, p.tiles_y strips per image,
 // p.ntiles threads in all
-template <typename T, int S>
+template <typename T, int S, bool SILU = false>      // SILU: + SiLU instead of the ReLU (UDP_ACT_SILU)
 __global__ __launch_bounds__(256) void dwconv3_kernel(const ConvParams p) {
   constexpr int V = DwTr<T>::V;
   long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -167,7 +118,7 @@ __global__ __launch_bounds__(256) void dwconv3_kernel(const ConvParams p) {
   };
   auto finish = [&](int oy, const float (&a)[V]) __attribute__((always_inline)) {
     const size_t pix = img_out + (size_t)oy * p.Wout + ox;
-    dw_store<T, V>(p, pix, c, a);
+    dw_store<T, V, SILU>(p, pix, c, a);
     if (p.nout2) dw_passthrough<T>(p, pix, c);
   };
 
@@ -215,7 +166,7 @@ __global__ __launch_bounds__(256) void dwconv3_kernel(const ConvParams p) {
 // L1 / L2 (the maps where K > 3 occurs are 64 x 48 and smaller, the weights K * K * C * 4 bytes).  Same arithmetic
 // contract as above: bias, then one fmaf per tap in the order ky, kx, taps outside the image skipped.
 // thread = (image, output row, output column, channel group); p.ntiles threads in all
-template <typename T, int S, int K>
+template <typename T, int S, int K, bool SILU = false>
 __global__ __launch_bounds__(256) void dwconvk_kernel(const ConvParams p) {
   constexpr int V = DwTr<T>::V, PAD = K / 2;
   long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -258,7 +209,7 @@ __global__ __launch_bounds__(256) void dwconvk_kernel(const ConvParams p) {
     }
   }
   const size_t pix = ((size_t)n * p.Hout + oy) * p.Wout + ox;
-  dw_store<T, V>(p, pix, c, a);
+  dw_store<T, V, SILU>(p, pix, c, a);
   if (p.nout2) dw_passthrough<T>(p, pix, c);
 }
 
@@ -384,7 +335,7 @@ int dwconv_validate(const udp_conv_op& o, int dtype) {
   if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "depthwise conv: dtype %d", dtype);
   if ((o.ks != 3 && o.ks != 5 && o.ks != 7) || (o.stride != 1 && o.stride != 2) || o.cin <= 0 || o.cin != o.cout || o.cin % 32 || o.cout_pad != o.cout)
     return fail(UDP_ERR_ARG, "depthwise conv: 3x3 | 5x5 | 7x7, stride 1 | 2, cin == cout == cout_pad, a multiple of 32 (k%d C%d->%d)", o.ks, o.cin, o.cout);
-  if (o.relu < 0 || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "depthwise conv: activation code %d", o.relu);
+  if (o.relu < 0 || o.relu > UDP_ACT_SILU || o.relu == 3) return fail(UDP_ERR_ARG, "depthwise conv: activation code %d", o.relu);
   if (o.relu == UDP_ACT_HSWISH) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: no hard-swish epilogue (activation code 2)");
   if (o.hin < 1 || o.win < 1 || o.hout != (o.hin - 1) / o.stride + 1 || o.wout != (o.win - 1) / o.stride + 1)
     return fail(UDP_ERR_ARG, "depthwise conv: %dx%d -> %dx%d does not match stride %d", o.hin, o.win, o.hout, o.wout, o.stride);
@@ -418,7 +369,7 @@ int se_validate(const udp_conv_op& o, int dtype) {
   const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
   if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
     return fail(UDP_ERR_ARG, "squeeze-excitation: channel views");
-  if (o.relu < 0 || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "squeeze-excitation: activation code %d", o.relu);
+  if (o.relu < 0 || o.relu > UDP_ACT_SILU || o.relu == 3) return fail(UDP_ERR_ARG, "squeeze-excitation: activation code %d", o.relu);
   if (o.n_up || o.n_out2 || o.group || o.in_stuff2 || o.wfmt || o.relu || o.out_buf == UDP_BUF_OUTPUT)
     return fail(UDP_ERR_UNSUPPORTED, "squeeze-excitation: no addends, activation, second outputs, groups or NCHW output");
   return UDP_OK;
@@ -433,7 +384,7 @@ int pixshuf_validate(const udp_conv_op& o, int dtype) {
   const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
   if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
     return fail(UDP_ERR_ARG, "pixel shuffle: channel views");
-  if (o.relu < 0 || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "pixel shuffle: activation code %d", o.relu);
+  if (o.relu < 0 || o.relu > UDP_ACT_SILU || o.relu == 3) return fail(UDP_ERR_ARG, "pixel shuffle: activation code %d", o.relu);
   if (o.n_up || o.n_out2 || o.chain_cout || o.group || o.in_stuff2 || o.relu || o.out_buf == UDP_BUF_OUTPUT)
     return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: pure data movement (no addends, ReLU, second outputs or NCHW output)");
   return UDP_OK;
@@ -446,12 +397,13 @@ int describe_dwconv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
   if (!p.in || !p.out || !p.wgt || !p.bias || (p.nout2 && (!p.res || !p.out2[0])) || (!p.nout2 && p.res))
     return fail(UDP_ERR_ARG, "depthwise conv: null pointer (or a residual without a passthrough)");
   const int V = dtype == UDP_F32 ? 4 : 8;
+  const bool si = p.relu == UDP_ACT_SILU;      // the SiLU instantiations
   if (ks != 3) {      // 5x5 / 7x7: one output pixel x V channels per thread (dwconvk_kernel)
     if ((ks != 5 && ks != 7) || (stride != 1 && stride != 2)) return fail(UDP_ERR_ARG, "depthwise conv: ks %d stride %d", ks, stride);
     const long total = (long)p.N * p.Hout * p.Wout * (p.Cin / V);
     if (total <= 0 || total >= (1L << 31) - 256) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: %ld threads; split the batch", total);
     p.ntiles = (int)total;
-#define UDP_DWK(T, S, K) reinterpret_cast<const void*>(&dwconvk_kernel<T, S, K>)
+#define UDP_DWK(T, S, K) (si ? reinterpret_cast<const void*>(&dwconvk_kernel<T, S, K, true>) : reinterpret_cast<const void*>(&dwconvk_kernel<T, S, K>))
     out->fn = dtype == UDP_F32 ? (ks == 5 ? (stride == 1 ? UDP_DWK(float, 1, 5) : UDP_DWK(float, 2, 5)) : (stride == 1 ? UDP_DWK(float, 1, 7) : UDP_DWK(float, 2, 7)))
                                : (ks == 5 ? (stride == 1 ? UDP_DWK(H2, 1, 5) : UDP_DWK(H2, 2, 5)) : (stride == 1 ? UDP_DWK(H2, 1, 7) : UDP_DWK(H2, 2, 7)));
 #undef UDP_DWK
@@ -470,8 +422,9 @@ int describe_dwconv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
   const long total = per_row * p.tiles_y;
   if (total <= 0 || total >= (1L << 31) - 256) return fail(UDP_ERR_UNSUPPORTED, "depthwise conv: %ld threads; split the batch", total);
   p.ntiles = (int)total;
-  out->fn = dtype == UDP_F32 ? (stride == 1 ? reinterpret_cast<const void*>(&dwconv3_kernel<float, 1>) : reinterpret_cast<const void*>(&dwconv3_kernel<float, 2>))
-                             : (stride == 1 ? reinterpret_cast<const void*>(&dwconv3_kernel<H2, 1>) : reinterpret_cast<const void*>(&dwconv3_kernel<H2, 2>));
+#define UDP_DW3(T, S) (si ? reinterpret_cast<const void*>(&dwconv3_kernel<T, S, true>) : reinterpret_cast<const void*>(&dwconv3_kernel<T, S>))
+  out->fn = dtype == UDP_F32 ? (stride == 1 ? UDP_DW3(float, 1) : UDP_DW3(float, 2)) : (stride == 1 ? UDP_DW3(H2, 1) : UDP_DW3(H2, 2));
+#undef UDP_DW3
   out->grid = dim3((unsigned)((total + 255) / 256));
   out->block = dim3(256);
   out->lds = 0;

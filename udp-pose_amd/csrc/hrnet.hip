@@ -56,16 +56,20 @@ struct udp_hrnet {
 
 static size_t esize(int dtype) { return dtype == UDP_BF16 ? 2 : 4; }   // bytes per stored element (F16X2: hi + lo)
 
-// udp_conv_op.relu as an activation code (udp_pose_hip.h, UDP_ACT_*).  Hard-swish exists as separate instantiations of
-// the stem kernels and of the plain 1x1 stride-1 NHWC convs only; everywhere else it is refused, never read as a ReLU.
+// udp_conv_op.relu as an activation code (udp_pose_hip.h, UDP_ACT_*).  Hard-swish and SiLU exist as separate
+// instantiations of the stem kernels and of the plain 1x1 stride-1 NHWC convs (SiLU: of the depthwise convs too) only;
+// everywhere else they are refused, never read as a ReLU.  Code 3 is not assigned.
 static int act_validate(const udp_conv_op& o, int dtype, bool has_res) {
-  if (o.relu < UDP_ACT_NONE || o.relu > UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "activation code %d (0 none, 1 ReLU, 2 hard-swish)", o.relu);
-  if (o.relu != UDP_ACT_HSWISH) return UDP_OK;
+  if (o.relu < UDP_ACT_NONE || o.relu > UDP_ACT_SILU || o.relu == 3)
+    return fail(UDP_ERR_ARG, "activation code %d (0 none, 1 ReLU, 2 hard-swish, 4 SiLU)", o.relu);
+  if (o.relu < UDP_ACT_HSWISH) return UDP_OK;
+  if (o.relu == UDP_ACT_SILU && o.kind == UDP_OP_DWCONV) return UDP_OK;      // (dwconv_validate refuses bf16)
   const bool plain1x1 = o.kind == UDP_OP_CONV && o.ks == 1 && o.stride == 1 && !o.group && !o.chain_cout && !o.n_up && !o.n_out2 && !has_res &&
                         !o.in_stuff2 && o.out_buf != UDP_BUF_OUTPUT;
   if (dtype == UDP_BF16 || (o.kind != UDP_OP_STEM && !plain1x1))
-    return fail(UDP_ERR_UNSUPPORTED, "hard-swish (activation code 2): UDP_OP_STEM and 1x1 stride-1 NHWC UDP_OP_CONV without addends, second outputs, "
-                "chain or group, in f32 / f16x2 only (kind %d, ks %d, stride %d)", o.kind, o.ks, o.stride);
+    return fail(UDP_ERR_UNSUPPORTED, "%s: UDP_OP_STEM and 1x1 stride-1 NHWC UDP_OP_CONV without addends, second outputs, "
+                "chain or group, in f32 / f16x2 only (kind %d, ks %d, stride %d)",
+                o.relu == UDP_ACT_SILU ? "SiLU (activation code 4; also UDP_OP_DWCONV)" : "hard-swish (activation code 2)", o.kind, o.ks, o.stride);
   return UDP_OK;
 }
 
@@ -73,7 +77,7 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
   const int nb = (int)h->buf_elems.size();
   auto buf_ok = [&](int b, int64_t need) { return b >= 0 && b < nb && h->buf_elems[b] >= need; };
   const int64_t out_need = (int64_t)o.hout * o.wout * (o.out_pitch ? o.out_pitch : o.cout);
-  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_SE) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_LINATTN) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
   if (const int rc = act_validate(o, h->dtype, o.res_buf != UDP_BUF_NONE)) return rc;
   if (o.lane < 0 || o.lane >= UDP_MAX_LANES || o.n_wait < 0 || o.n_wait > UDP_MAX_WAIT) return fail(UDP_ERR_ARG, "op %d: lane/n_wait", idx);
   for (int k = 0; k < o.n_wait; ++k)
@@ -124,6 +128,20 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
     const size_t wbytes = ((size_t)2 * o.cin * o.chain_cout + o.chain_cout) * 4;
     if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15))
       return fail(UDP_ERR_ARG, "op %d: squeeze-excitation parameter block outside the blob or misaligned", idx);
+    return UDP_OK;
+  }
+  if (o.kind == UDP_OP_GNORM || o.kind == UDP_OP_LINATTN) {
+    // GroupNorm(1, C) / the separable self-attention core (attn.hip); the norm's `out` may be the very view `in` is
+    const bool gn = o.kind == UDP_OP_GNORM;
+    const int rc = gn ? gnorm_validate(o, h->dtype) : linattn_validate(o, h->dtype);
+    if (rc) return rc;
+    const int ipitch = o.in_pitch ? o.in_pitch : o.cin;
+    if (!buf_ok(o.in_buf, (int64_t)o.hin * o.win * ipitch) || !buf_ok(o.out_buf, out_need) || o.res_buf != UDP_BUF_NONE)
+      return fail(UDP_ERR_ARG, "op %d: %s buffers missing or too small (or a residual)", idx, gn ? "group norm" : "linear attention");
+    if (o.in_buf == o.out_buf && (!gn || o.in_coff != o.out_coff || ipitch != (o.out_pitch ? o.out_pitch : o.cout)))
+      return fail(UDP_ERR_ARG, "op %d: %s", idx, gn ? "group norm in place needs the same view for in and out" : "linear attention: out must not be in");
+    if (gn && (o.w_off < 0 || (size_t)o.w_off + (size_t)2 * o.cin * 4 > h->weights_bytes || (o.w_off & 15)))
+      return fail(UDP_ERR_ARG, "op %d: group norm parameter block outside the blob or misaligned", idx);
     return UDP_OK;
   }
   if (o.kind == UDP_OP_DWCONV || o.kind == UDP_OP_PIXSHUF) {
@@ -262,6 +280,7 @@ extern "C" int udp_f16x2_overflow(void* stream, int reset) {
   if (!rc) rc = psa_h2_overflow(s, reset, &flag);
   if (!rc) rc = deconv_h2_overflow(s, reset, &flag);
   if (!rc) rc = dwconv_h2_overflow(s, reset, &flag);
+  if (!rc) rc = attn_h2_overflow(s, reset, &flag);
   return rc ? rc : flag;
 }
 
@@ -306,6 +325,7 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
     if (ops[i].kind == UDP_OP_DECONV) h->flops += 2.0 * 4 * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;   // 2x2 taps per output pixel
     if (ops[i].kind == UDP_OP_DWCONV) h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cout * ops[i].hout * ops[i].wout;   // ks * ks MACs per output element
     if (ops[i].kind == UDP_OP_SE) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // the two small products (pool and scale are not counted)
+    if (ops[i].kind == UDP_OP_LINATTN) h->flops += 2.0 * ops[i].cout * ops[i].hout * ops[i].wout;   // the weighted sum of the keys (soft-max and gate are not counted)
     if (ops[i].kind == UDP_OP_CONV && ops[i].chain_cout) h->flops += 2.0 * ops[i].cout * ops[i].chain_cout * ops[i].hout * ops[i].wout;
     h->ops.push_back(ops[i]);
   }
@@ -429,9 +449,9 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       p.up_shift[2] = o.chain_relu;
     }
     if (o.kind == UDP_OP_DWCONV) p.up_shift[0] = o.chain_cout;   // passthrough: real channels per half (n_up == 0)
-    if (o.kind == UDP_OP_SE) {
+    if (o.kind == UDP_OP_SE || o.kind == UDP_OP_GNORM) {
       p.wgt = h->weights + o.w_off;
-      p.up_shift[0] = o.chain_cout;                              // hidden width
+      p.up_shift[0] = o.chain_cout;                              // hidden width / real channels
     }
     if (o.kind == UDP_OP_BLOCK) {
       p.wgt = h->weights + o.w_off;
@@ -457,6 +477,8 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       case UDP_OP_DECONV: rc = describe_deconv(p, h->dtype, &ls[i]); break;
       case UDP_OP_DWCONV: rc = describe_dwconv(p, h->dtype, o.ks, o.stride, &ls[i]); break;
       case UDP_OP_SE: rc = describe_se(p, h->dtype, &ls[i]); break;
+      case UDP_OP_GNORM: rc = describe_gnorm(p, h->dtype, &ls[i]); break;
+      case UDP_OP_LINATTN: rc = describe_linattn(p, h->dtype, &ls[i]); break;
       case UDP_OP_PIXSHUF: rc = describe_pixshuf(p, h->dtype, &ls[i]); break;
       default:
         if (o.chain_cout) {
@@ -793,16 +815,24 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (dtype != UDP_F32 && dtype != UDP_BF16 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "udp_conv2d_fused: dtype %d", dtype);
   if (n <= 0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: n=%d", n);
   if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV && o->kind != UDP_OP_DWCONV && o->kind != UDP_OP_PIXSHUF &&
-      o->kind != UDP_OP_SE)
+      o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LINATTN)
     return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
   if (const int rc = act_validate(*o, dtype, res != nullptr)) return rc;
-  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && (!weights || (!bias && o->kind != UDP_OP_SE))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && o->kind != UDP_OP_LINATTN && (!weights || (!bias && o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
   if (o->kind == UDP_OP_SE) {
     const int rc = se_validate(*o, dtype);
     if (rc) return rc;
     if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation takes no residual");
     if (in == out && (o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
       return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation in place needs the same view for in and out");
+  }
+  if (o->kind == UDP_OP_GNORM || o->kind == UDP_OP_LINATTN) {
+    const bool gn = o->kind == UDP_OP_GNORM;
+    const int rc = gn ? gnorm_validate(*o, dtype) : linattn_validate(*o, dtype);
+    if (rc) return rc;
+    if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: %s takes no residual", gn ? "group norm" : "linear attention");
+    if (in == out && (!gn || o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
+      return fail(UDP_ERR_ARG, "udp_conv2d_fused: %s", gn ? "group norm in place needs the same view for in and out" : "linear attention: out must not be in");
   }
   if (o->kind == UDP_OP_DWCONV || o->kind == UDP_OP_PIXSHUF) {
     const bool dw = o->kind == UDP_OP_DWCONV;
@@ -836,8 +866,8 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   p.Cout = o->cout;
   p.CoutPad = o->cout_pad;
   p.relu = o->relu;
-  if (o->kind == UDP_OP_SE) {
-    p.up_shift[0] = o->chain_cout;      // hidden width (se_validate: n_up == 0, n_out2 == 0)
+  if (o->kind == UDP_OP_SE || o->kind == UDP_OP_GNORM) {
+    p.up_shift[0] = o->chain_cout;      // hidden width / real channels (se_validate, gnorm_validate: n_up == 0, n_out2 == 0)
   } else if (o->kind == UDP_OP_DWCONV) {
     if (o->n_out2) {
       p.nout2 = 1;
@@ -891,6 +921,8 @@ static int conv2d_fused_impl(const udp_conv_op* o, int dtype, int n, const void*
                  : o->kind == UDP_OP_DECONV ? describe_deconv(p, dtype, &l)
                  : o->kind == UDP_OP_DWCONV ? describe_dwconv(p, dtype, o->ks, o->stride, &l)
                  : o->kind == UDP_OP_SE     ? describe_se(p, dtype, &l)
+                 : o->kind == UDP_OP_GNORM  ? describe_gnorm(p, dtype, &l)
+                 : o->kind == UDP_OP_LINATTN ? describe_linattn(p, dtype, &l)
                  : o->kind == UDP_OP_PIXSHUF ? describe_pixshuf(p, dtype, &l)
                                             : describe_conv(p, dtype, o->ks, o->stride, &l);
   if (rc) return rc;
@@ -919,7 +951,7 @@ extern "C" int udp_conv2d_fused_group(udp_conv_item* items, int n_items, int dty
     const udp_conv_op* o = it.op;
     if (!o || o->kind != UDP_OP_CONV || o->n_up || o->out_buf == UDP_BUF_OUTPUT)
       return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused_group: member %d is not a plain NHWC conv", j);
-    if (o->relu == UDP_ACT_HSWISH) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused_group: member %d: hard-swish has no merged-launch form", j);
+    if (o->relu >= UDP_ACT_HSWISH) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused_group: member %d: hard-swish / SiLU have no merged-launch form", j);
     if (it.bn_ws && (dtype == UDP_F16X2 || o->relu || it.res || (o->out_pitch && o->out_pitch != o->cout) || o->out_coff))
       return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused_group: member %d: BatchNorm sums need a plain fp32 / bf16 conv", j);
     ConvParams p;

@@ -74,9 +74,10 @@ class ShuffleNetV2Program(Program):
 
     # ------------------------------------------------------------------ op helpers
     def _pw(self, name, x, w, b, relu, in_map=None, cin_t=None, out_map=None, cout_t=None, in_view=None, into=None,
-            to_output=False):
+            to_output=False, res=None):
         """One dense conv (1x1 / 3x3, stride 1) from an already folded weight, with the channel maps of ``_pack``.
-        ``in_view = cin``: read the first ``cin`` channels of a wider ``x``; ``into = (tensor, coff)``."""
+        ``in_view = cin``: read the first ``cin`` channels of a wider ``x``; ``into = (tensor, coff)``; ``res``: a tensor
+        of the output's shape added in the epilogue (the MobileViTv2 planner's residuals)."""
         ks = int(w.shape[2])
         head_ws = to_output and os.environ.get("UDP_POSE_HEAD_WS", "1") != "0"
         ws = self.use_ws and (not to_output or head_ws)
@@ -93,14 +94,18 @@ class ShuffleNetV2Program(Program):
             if (out.h, out.w) != (x.h, x.w) or into[1] + cout > out.c:
                 raise ValueError("%s: output slice does not fit its tensor" % name)
             views.update(out_coff=into[1], out_pitch=out.c)
+        if res is not None:
+            if (res.c, res.h, res.w) != (cout, x.h, x.w):
+                raise ValueError("%s: residual does not match the output" % name)
+            views.update(res=res)
         self._emit(_lib.UDP_OP_CONV, name, x, out, ks=ks, stride=1, relu=relu, cin=cin, cout=cout, cout_pad=cout_pad,
                    hout=x.h, wout=x.w, w_off=w_off, b_off=b_off, wfmt=int(ws), wexp=wexp, **views)
         return out
 
-    def _dw(self, conv, bn, x, cin, pos, stride, into=None, passthrough=None):
+    def _dw(self, conv, bn, x, cin, pos, stride, into=None, passthrough=None, act=0):
         """Depthwise k x k conv (k = 3, or 5 / 7 in the ShuffleNetV2+ planner) + BatchNorm on the first ``cin`` stored
         channels of ``x``; ``pos[j]``: where logical channel j of the [C,1,k,k] weight sits.  ``into = (tensor, coff)``; ``passthrough = (src, dst, r)``: the
-        x_proj copy of a stride-1 unit (include/udp_pose_hip.h, UDP_OP_DWCONV)."""
+        x_proj copy of a stride-1 unit (include/udp_pose_hip.h, UDP_OP_DWCONV); ``act``: the activation code."""
         w, b = self._fold(conv, bn)
         ks = int(w.shape[2])
         if tuple(w.shape[1:]) != (1, ks, ks) or ks not in self.DW_KERNELS or w.shape[0] != len(pos):
@@ -123,7 +128,7 @@ class ShuffleNetV2Program(Program):
             # ops_array() can zip it with ``out2`` and _reads() sees the dependency -- the kernel never reads add2;
             # ``chain_cout`` carries r, no chained conv
             views.update(res=src, res_coff=0, res_pitch=src.c, res_c=src.c, out2=[(dst, 0)], add2=[(src, 0)], chain_cout=r)
-        self._emit(_lib.UDP_OP_DWCONV, conv, x, out, ks=ks, stride=stride, relu=0, cin=cin, cout=cin, cout_pad=cin, hout=ho, wout=wo,
+        self._emit(_lib.UDP_OP_DWCONV, conv, x, out, ks=ks, stride=stride, relu=act, cin=cin, cout=cin, cout_pad=cin, hout=ho, wout=wo,
                    w_off=self._put(wp.numpy().tobytes()), b_off=self._put(bp.numpy().tobytes()), **views)
         return out
 
