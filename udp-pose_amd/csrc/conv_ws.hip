@@ -18,7 +18,12 @@ namespace udp {
 //   workgroup = 4 waves = CP cout pairs x PG = 4/CP pixel groups; wave (cp, pg) computes pixel blocks
 //   pg*PB .. pg*PB+PB-1 of the tile (M <= 16*PB*PG pixels) x couts (blockIdx.y*CP + cp)*32 .. +31.
 // ---------------------------------------------------------------------------------------------
-// residual of one pixel block (8 consecutive split-fp16 channels per lane) held raw from the prologue to the epilogue
+// UDP_WS_LATE_RES (compile time, default 1; 0 = the earlier placement, for A/B builds): the 3x3 stride-1 bodies request the
+// residual at the head of the last three steps (the peeled tail of the step loop) instead of in the prologue
+#ifndef UDP_WS_LATE_RES
+#define UDP_WS_LATE_RES 1
+#endif
+// residual of one pixel block (8 consecutive split-fp16 channels per lane), raw until the epilogue adds it
 template <int NB>
 struct ResH2 {
   u32x4 hi[NB / 2], lo[NB / 2];
@@ -38,7 +43,8 @@ __device__ __forceinline__ void add_res_h2(f32x4 (&v)[NB], const ResH2<NB>& o) {
 }
 
 // HS: the hard-swish / SiLU instantiations (HS = udp_conv_op.relu = UDP_ACT_HSWISH | UDP_ACT_SILU; conv_ws_hs_kernel below)
-template <int KS, int STRIDE, int PB, int CP, bool NCHW, bool OUT2 = false, int HS = 0>
+// NUP = false: a body for convs without up-sampled addends (udp_conv_op.n_up == 0), which then keeps no pixel coordinates
+template <int KS, int STRIDE, int PB, int CP, bool NCHW, bool OUT2 = false, int HS = 0, bool NUP = true>
 __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile_id, const int cby) {
   using T = H2;
   constexpr int CK = 32, ESZ = 2, NB = 2, NW = 4;
@@ -173,7 +179,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   stage(0, smem);      // chunk 0 is on its way while the rest of the per-lane state is set up
 
   // ---- the lane's PB output pixels
-  int prow[PB], opix[PB], ocrd[PB];
+  int prow[PB], opix[PB], ocrd[NCHW || NUP ? PB : 1];
 #pragma unroll
   for (int i = 0; i < PB; ++i) {
     const int m0 = (pg * PB + i) * 16 + li;
@@ -187,7 +193,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
     const bool ok = m0 < M && n < p.N && y < p.Hout && xo < p.Wout && (NCHW || cbase < p.Cout);
     const unsigned pix = __umul24(__umul24(n, p.Hout) + y, p.Wout) + xo;
     opix[i] = ok ? (int)pix : -1;
-    ocrd[i] = ok ? (y | (xo << 10) | (n << 20)) : -1;
+    if constexpr (NCHW || NUP) ocrd[i] = ok ? (y | (xo << 10) | (n << 20)) : -1;
   }
 
   // ONE accumulator set: the weights are stored scaled by 2^wexp (power of two, exact) so that their largest
@@ -206,37 +212,58 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   // residual: issued right behind the chunk-0 DMA (no res: a zero-length descriptor, the loads return zeros -- no
   // branch around loads, see the A ring), added in the epilogue.  The barriers keep hipcc from moving these loads in
   // front of the DMA: the first wait below counts them as YOUNGER than it.
+  //
+  // LATE (3x3 stride 1): the residual is only needed after the last MFMA, and between the DMA and the first MFMA its
+  // PB * NB loads -- in MFMA fragment order, a cache line per lane -- stand in front of the loop while their PB * 8
+  // registers are held through all of it.  So the last three steps (taps 6, 7, 8 of the last chunk: exactly the last
+  // trip of the ring of three) are peeled out of the step loop as straight-line code, and the residual is requested at
+  // the head of that tail, right behind the tail's only A loads (the fragments of tap 8; taps 6 and 7 were fetched at
+  // taps 4 and 5): no A fragment queues behind it, and nothing in the tail waits for it -- the tail has no tap-0 wait,
+  // the last chunk's DMA was waited for at its tap 0 (or, with one stage buffer, by the refill's vmcnt(0)).  Still
+  // unconditional loads against the zero-length descriptor when there is no residual.
+  constexpr bool LATE = UDP_WS_LATE_RES && KS == 3 && STRIDE == 1 && !NCHW && AD == 3;
   constexpr int NR = NCHW ? 0 : PB * NB;          // buffer loads per lane
   ResH2<NB> rres[NCHW ? 1 : PB];
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  if constexpr (!NCHW) {
+  // (8 blocks: the second half of the blocks at the head of tap 7, where no A load is issued either and the ring slot of
+  // tap 6 is free -- all 16 at tap 6 next to the full A ring exceed the 256 registers)
+  constexpr int RSPLIT = LATE && PB > 6 ? PB / 2 : PB;
+  auto load_res = [&](auto I0, auto I1) __attribute__((always_inline)) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < PB; ++i)
+    for (int i = decltype(I0)::value; i < (NCHW ? 0 : decltype(I1)::value); ++i)
       load_res_h2(rres[i], r_res, opix[i] >= 0 ? (unsigned)opix[i] * respb + (p.res_coff + cbase) * ESZ : kOobOff, res_lo);
-  }
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  if constexpr (!LATE) load_res(std::integral_constant<int, 0>{}, std::integral_constant<int, PB>{});
 
   UDP_STAMP(2);
   int c = 0, tap = 0;                     // chunk / tap of the current step
   const unsigned char* sb = smem;
-  auto step = [&](auto BUFC, int s) __attribute__((always_inline)) {
-    constexpr int BUF = decltype(BUFC)::value;
+  // TAIL: -1 inside the step loop; 0, 1, 2 = taps 6, 7, 8 of the last chunk in the peeled tail (LATE only)
+  auto step = [&](auto BUFC, auto TAILC, int s) __attribute__((always_inline)) {
+    constexpr int BUF = decltype(BUFC)::value, TAIL = decltype(TAILC)::value;
     // the A loads go first: vector-memory operations complete in issue order, fragments queued behind the
     // next chunk's DMA would wait for it
     // (issued unconditionally -- past the end the last step's fragments are fetched again: a prefetch under a
-    // branch makes hipcc assume nothing newer is in flight and wait with vmcnt(0) at every use)
+    // branch makes hipcc assume nothing newer is in flight and wait with vmcnt(0) at every use.  LATE: the loop never
+    // runs past the end, and the tail knows where it is -- tap 6 fetches the last step's fragments, taps 7 and 8 nothing)
 #if !(UDP_WS_DBG & 1)
-    load_a(s + AD - 1 < nsteps ? s + AD - 1 : nsteps - 1, ah[(BUF + AD - 1) % AD], al[(BUF + AD - 1) % AD]);
+    if constexpr (!LATE)
+      load_a(s + AD - 1 < nsteps ? s + AD - 1 : nsteps - 1, ah[(BUF + AD - 1) % AD], al[(BUF + AD - 1) % AD]);
+    else if constexpr (TAIL <= 0)
+      load_a(s + AD - 1, ah[(BUF + AD - 1) % AD], al[(BUF + AD - 1) % AD]);
 #endif
-    if (tap == 0) {
+    if constexpr (TAIL == 0) load_res(std::integral_constant<int, 0>{}, std::integral_constant<int, RSPLIT>{});
+    if constexpr (TAIL == 1 && RSPLIT < PB) load_res(std::integral_constant<int, RSPLIT>{}, std::integral_constant<int, PB>{});
+    if (TAIL < 0 && tap == 0) {
       // chunk c's DMA has landed (vector-memory operations complete in issue order: all but the 2*NB A loads
       // just issued, which may stay in flight; letting the previous step's stay in flight too changes nothing)
       if (c == 1) UDP_STAMP(9);                           // (diagnostic builds only: chunk-boundary stamps of chunks 1, 2, 4)
       if (c == 2) UDP_STAMP(11);
       if (c == 4) UDP_STAMP(13);
-      // (at s == 0 the residual loads, issued behind the chunk-0 DMA, may stay in flight as well)
+      // (at s == 0 the residual loads, where the prologue issued them behind the chunk-0 DMA, may stay in flight as well)
       bool refill = false;
       if constexpr (STRIDE == 2 || OUT2) refill = p.sbuf && c > 0;   // (not in the merged kernel: its members keep two stages)
       if (refill) {
@@ -251,7 +278,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
         sb = smem;
       } else {
         if (s == 0)
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NB + NR) : "memory");
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NB + (LATE ? 0 : NR)) : "memory");
         else
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NB) : "memory");
         if (s == 0) UDP_STAMP(3);
@@ -272,7 +299,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
     f16x8 a2[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) a2[nb] = ah[BUF][nb] * (_Float16)0x1p-11f;
-    const int tap_rows = KS == 1 ? 0 : (tap / KS) * IW + tap % KS;
+    const int tap_rows = KS == 1 ? 0 : TAIL >= 0 ? (KS - 1) * IW + TAIL : (tap / KS) * IW + tap % KS;
     // B fragments (hi, lo) in a ring of three: the LDS reads of block i + 2 are issued before the MFMAs of
     // block i (one wave per SIMD has nothing else to cover the ~200-cycle LDS latency with)
     f16x8 xh[3], xl[3];
@@ -301,18 +328,33 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
       for (int nb = 0; nb < NB; ++nb) acc[i][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[nb], xl[i % 3], acc[i][nb], 0, 0, 0);
 #endif
     }
-    if (++tap == TAPS) {
-      tap = 0;
-      ++c;
+    if constexpr (TAIL < 0) {
+      if (++tap == TAPS) {
+        tap = 0;
+        ++c;
+      }
     }
   };
-  for (int s = 0; s < nsteps; s += AD) {
-    step(std::integral_constant<int, 0>{}, s);
-    if (s + 1 < nsteps) step(std::integral_constant<int, 1>{}, s + 1);
-    if (s + 2 < nsteps) step(std::integral_constant<int, 2>{}, s + 2);
-    if constexpr (AD > 3) if (s + 3 < nsteps) step(std::integral_constant<int, 3>{}, s + 3);
-    if constexpr (AD > 4) if (s + 4 < nsteps) step(std::integral_constant<int, 4>{}, s + 4);
-    if constexpr (AD > 5) if (s + 5 < nsteps) step(std::integral_constant<int, 5>{}, s + 5);
+  constexpr std::integral_constant<int, -1> LOOP{};
+  if constexpr (LATE) {
+    // nsteps = 9 * nchunks: whole trips of the ring of three, the last of them peeled (sb stays the last chunk's stage)
+    for (int s = 0; s < nsteps - AD; s += AD) {
+      step(std::integral_constant<int, 0>{}, LOOP, s);
+      step(std::integral_constant<int, 1>{}, LOOP, s + 1);
+      step(std::integral_constant<int, 2>{}, LOOP, s + 2);
+    }
+    step(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, nsteps - 3);
+    step(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, nsteps - 2);
+    step(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, nsteps - 1);
+  } else {
+    for (int s = 0; s < nsteps; s += AD) {
+      step(std::integral_constant<int, 0>{}, LOOP, s);
+      if (s + 1 < nsteps) step(std::integral_constant<int, 1>{}, LOOP, s + 1);
+      if (s + 2 < nsteps) step(std::integral_constant<int, 2>{}, LOOP, s + 2);
+      if constexpr (AD > 3) if (s + 3 < nsteps) step(std::integral_constant<int, 3>{}, LOOP, s + 3);
+      if constexpr (AD > 4) if (s + 4 < nsteps) step(std::integral_constant<int, 4>{}, LOOP, s + 4);
+      if constexpr (AD > 5) if (s + 5 < nsteps) step(std::integral_constant<int, 5>{}, LOOP, s + 5);
+    }
   }
   UDP_STAMP(5);
   // conv = acc * 2^-wexp; + bias; + residual (hi + lo * 2^-11)
@@ -348,8 +390,8 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
         }
     } else {
       const unsigned ooff = opix[i] >= 0 ? (unsigned)opix[i] * outpb + (p.out_coff + cbase) * ESZ : kOobOff;
-      if (p.nup) {   // wave-uniform, rare (exchange-unit outputs only)
-        const int crd = ocrd[i];
+      if (NUP && p.nup) {   // wave-uniform, rare (exchange-unit outputs only)
+        const int crd = ocrd[NUP ? i : 0];
         const int y = crd & 1023, xo = (crd >> 10) & 1023, n = crd >> 20;
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
@@ -455,11 +497,18 @@ __global__ __launch_bounds__(256, 2) void conv_ws_hs_kernel(const ConvParams p) 
 }
 
 // Merged launch of up to 4 independent weight-stationary convs (same-depth convs of different HRNet branches):
-// every member runs the 6-pixel-blocks-per-wave body with its own cout-pair split (ConvMulti::code = CP).
+// every member runs the 6-pixel-blocks-per-wave body with its own cout-pair split (ConvMulti::code = CP), or the
+// 8-block one-pair body (code 8, below).
 #ifndef UDP_WS_MPB
 #define UDP_WS_MPB 6      // pixel blocks per wave of the merged kernel's members
 #define UDP_WS_MOCC 2     // workgroups per CU the merged kernel is compiled for (waves per SIMD)
 #endif
+// A one-pair (32 output channels) 3x3 member may run 8 pixel blocks per wave instead: 512-pixel tiles, a third more
+// pixels under the same per-wave fixed cost.  ConvMulti::code = 8, code field 3 of a table entry.  The registers for
+// two more blocks of accumulators and residual come from the late residual (conv_ws_body, LATE), so the arm exists
+// only in builds that have it.
+constexpr int kWsCode8 = 8;
+constexpr bool kWsHave8 = UDP_WS_MPB == 6 && UDP_WS_LATE_RES && UDP_WS_AD == 3;
 template <int KS>
 __global__ __launch_bounds__(256, UDP_WS_MOCC) void conv_ws_multi(const ConvMulti m) {
   const unsigned b = blockIdx.x;
@@ -485,11 +534,24 @@ __global__ __launch_bounds__(256, UDP_WS_MOCC) void conv_ws_multi(const ConvMult
     cby = __builtin_amdgcn_readfirstlane(cby);
     code = m.code[j];
   }
+  if constexpr (KS == 3 && kWsHave8) {
+    // one cout pair, 8 pixel blocks per wave (code field 3 of the table entry); 3x3 only, see describe_conv_ws
+    if (code == kWsCode8) {
+      conv_ws_body<KS, 1, 8, 1, false, false, 0, false>(m.p[j], tile, (int)cby);
+      return;
+    }
+  }
   switch (code) {
     case 1: conv_ws_body<KS, 1, UDP_WS_MPB, 1, false>(m.p[j], tile, (int)cby); break;
     case 2: conv_ws_body<KS, 1, UDP_WS_MPB, 2, false>(m.p[j], tile, (int)cby); break;
     default: conv_ws_body<KS, 1, UDP_WS_MPB, 4, false>(m.p[j], tile, (int)cby); break;
   }
+}
+
+// The 8-block body on a launch of its own: only for a conv that was described as a member of a merged launch and then
+// found no sibling to share it with (hrnet.hip, make_nodes).
+__global__ __launch_bounds__(256, 2) void conv_ws_pb8_kernel(const ConvParams p) {
+  conv_ws_body<3, 1, 8, 1, false, false, 0, false>(p, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // Weight-stationary split-fp16 conv (conv_ws_h2_kernel): tile choice + dispatch.  Returns 1 when the
@@ -517,6 +579,20 @@ static int describe_ws_pb(const ConvParams& p, int pb, int cp, size_t lds, Launc
   UDP_WS(2, 4) UDP_WS(3, 4) UDP_WS(4, 4) UDP_WS(6, 4)
 #undef UDP_WS
   return 1;
+}
+static int describe_ws_pb8(const ConvParams& p, size_t lds, Launch* out) {
+  static bool attr_set = false;
+  const void* kern = reinterpret_cast<const void*>(&conv_ws_pb8_kernel);
+  if (!attr_set) {
+    UDP_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  out->fn = kern;
+  out->grid = dim3(p.ntiles, p.CoutPad / 32);
+  out->block = dim3(256);
+  out->lds = (unsigned)lds;
+  out->p = p;
+  return UDP_OK;
 }
 template <int PB, int CP, int ACT>
 static int describe_ws_hs_one(const ConvParams& p, size_t lds, Launch* out) {
@@ -583,11 +659,15 @@ static bool ws_tile(const ConvParams& p, int ks, int stride, int cp, int pb, WsT
       lds /= 2;
     }
     if (lds > 160 * 1024) continue;
+    // the 8-block arm of the merged launch (describe_conv_ws offers it to one-pair members): only a tile that fills all 8
+    // blocks of every wave, tiles the map exactly, and leaves LDS for a second workgroup on the CU.  64x48: 3 column
+    // tiles of 16 x 32 rows -- halo 18 x 34 = 612 rows (39 of the 40 staging groups), 79,872 bytes
+    if (pb == 8 && (G * R * TW != maxM || p.Hout % R || TW * split != p.Wout || lds > 80 * 1024)) continue;
     // pixel blocks per wave the tile really needs (the halo limit may have shrunk it): the smallest instantiated
     // count that covers them, so no wave idles under masked blocks
     const int need = ceil_div(ceil_div(G * R * TW, 16), pg);
     if (need > pb) continue;
-    const int pbe = need <= 2 ? 2 : need <= 3 ? 3 : need <= 4 ? 4 : 6;
+    const int pbe = need <= 2 ? 2 : need <= 3 ? 3 : need <= 4 ? 4 : need <= 6 ? 6 : 8;
     const int tiles = ceil_div(p.N, G) * ceil_div(p.Hout, R) * ceil_div(p.Wout, TW);
     // score = useful pixels / pixel slots over the whole layer (ragged last tiles and masked blocks are waste)
     //         x the share of the staged halo tile that is not halo (narrow tiles stage more of it)
@@ -630,10 +710,15 @@ int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped
   const long min_wgs = grouped ? 0 : knob("UDP_POSE_WS_MINWGS", g_ws_fill_wgs);
   // candidates from the fattest wave tile down: the first one that fills the chip wins, else the one with
   // the most workgroups
+  // 8 blocks: one-pair 3x3 members of a merged launch only (ws_tile has the tile's conditions; two- and four-pair
+  // members would need 2 x 44 KB of stage buffers and keep 6).  UDP_POSE_WS_PB8=0: the chooser without this candidate
+  const bool offer8 = kWsHave8 && grouped && ks == 3 && stride == 1 && pairs % 2 == 1 && !p.out_nchw_f32 && !p.nout2 && !p.nup &&
+                      knob("UDP_POSE_WS_PB8", 1) != 0;
   WsTile best{}, t{};
   bool have = false;
-  for (int pb : {6, 4, 3, 2}) {
+  for (int pb : {8, 6, 4, 3, 2}) {
     for (int cp : {4, 2, 1}) {
+      if (pb == 8 && (!offer8 || cp != 1)) continue;
       if (pairs % cp || (force_cp && cp != force_cp) || (force_pb && pb != force_pb)) continue;
       if (grouped && stride == 1 && UDP_WS_MPB != 6 && pb != UDP_WS_MPB) continue;   // (diagnostic builds of the merged kernel)
       if (!ws_tile(p, ks, stride, cp, pb, &t, !grouped && !p.out_nchw_f32)) continue;   // (the NCHW-output kernels keep two stage buffers)
@@ -663,6 +748,9 @@ int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped
     fprintf(stderr, "ws conv k%d s%d %dx%d C%d->%d: G=%d R=%d TW=%d CP=%d PB=%d lds=%zu%s wgs=%d\n", ks, stride, p.Hout, p.Wout, p.Cin,
             p.Cout, p.G, p.R, p.TW, best.cp, best.pb, best.lds, best.sbuf ? " (one stage buffer)" : "", best.wgs);
   int rc = 1;
+  if (best.pb == 8) {
+    rc = describe_ws_pb8(p, best.lds, out);
+  } else
   if (ks == 3 && stride == 1 && !p.out_nchw_f32) rc = describe_ws_pb<3, 1, false>(p, best.pb, best.cp, best.lds, out);
   if (ks == 3 && stride == 1 && p.out_nchw_f32) rc = describe_ws_pb<3, 1, true>(p, best.pb, best.cp, best.lds, out);   // the net's NCHW fp32 output (RSN head)
   if (ks == 3 && stride == 2) rc = describe_ws_pb<3, 2, false>(p, best.pb, best.cp, best.lds, out);
@@ -673,8 +761,9 @@ int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped
   if (rc == 1) return fail(UDP_ERR_UNSUPPORTED, "weight-stationary conv: no kernel for PB=%d CP=%d", best.pb, best.cp);
   if (rc == UDP_OK && p.nout2 && !(ks == 3 && stride == 1))
     return fail(UDP_ERR_UNSUPPORTED, "second outputs: 3x3 stride-1 convs only");
-  if (rc == UDP_OK && grouped && best.pb == UDP_WS_MPB && stride == 1 && !p.nout2) {
-    out->groupable = 300 + ks * 10 + 6;        // storage/kernel family 3 = split fp16 weight-stationary
+  if (rc == UDP_OK && grouped && (best.pb == UDP_WS_MPB || best.pb == 8) && stride == 1 && !p.nout2) {
+    // storage/kernel family 3 = split fp16 weight-stationary; last digit: the member's pixel blocks per wave (6 and 8 share a launch)
+    out->groupable = 300 + ks * 10 + (best.pb == 8 ? 8 : 6);
     out->ws_cp = best.cp;
   }
   return rc;
@@ -750,7 +839,7 @@ static void ws_order(ConvMulti* m, int n) {
   m->tab_n = 0;
   bool ok = total % 8 == 0 && total / 8 <= (unsigned)kMultiTab && getenv("UDP_POSE_WS_NOTAB") == nullptr;
   for (int j = 0; j < n && ok; ++j)
-    ok = m->tiles[j] % 8 == 0 && m->ncby[j] <= 64 && m->tiles[j] < (1u << 22) && (m->code[j] == 1 || m->code[j] == 2 || m->code[j] == 4);
+    ok = m->tiles[j] % 8 == 0 && m->ncby[j] <= 64 && m->tiles[j] < (1u << 22) && (m->code[j] == 1 || m->code[j] == 2 || m->code[j] == 4 || m->code[j] == kWsCode8);
   for (size_t k = 0; k < segs.size() && ok; ++k) ok = segs[k].start % 8 == 0 && segs[k].first % 8 == 0;
   if (ok) {
     for (const Seg& sg : segs) {
@@ -758,7 +847,7 @@ static void ws_order(ConvMulti* m, int n) {
       for (unsigned b = sg.start; b < sg.start + sg.cnt; b += 8) {
         int tile, cby;
         ws_decode(b - sg.start + sg.first, m->tiles[j], m->ncby[j], tile, cby);
-        const unsigned cl = m->code[j] == 1 ? 0u : m->code[j] == 2 ? 1u : 2u;      // log2 of the member's CP
+        const unsigned cl = m->code[j] == 1 ? 0u : m->code[j] == 2 ? 1u : m->code[j] == 4 ? 2u : 3u;      // log2 of the member's code (CP; 3: the 8-block arm)
         m->tab[b >> 3] = (unsigned)j | (cl << 2) | ((unsigned)cby << 4) | ((unsigned)tile << 10);
       }
     }
@@ -831,12 +920,12 @@ int describe_ws_multi(const Launch* members, int n, ConvMulti* m, Launch* out) {
   memset(m, 0, sizeof(*m));
   unsigned total = 0, lds = 0;
   for (int j = 0; j < n; ++j) {
-    if (members[j].groupable != members[0].groupable) return fail(UDP_ERR_ARG, "describe_multi: mixed weight-stationary members");
+    if (members[j].groupable / 10 != members[0].groupable / 10) return fail(UDP_ERR_ARG, "describe_multi: mixed weight-stationary members");
     m->p[j] = members[j].p;
     m->start[j] = total;
     m->tiles[j] = members[j].grid.x;
     m->ncby[j] = members[j].grid.y;
-    m->code[j] = members[j].ws_cp;
+    m->code[j] = members[j].groupable % 10 == 8 ? kWsCode8 : members[j].ws_cp;
     total += members[j].grid.x * members[j].grid.y;
     if (members[j].lds > lds) lds = members[j].lds;
   }
