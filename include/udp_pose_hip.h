@@ -186,7 +186,60 @@ enum udp_op_kind {
    * class (class pixels g, g + G, ... in raster order) that are then added in the order g = 0 .. G-1; G depends on C
    * only, nothing is atomic: an image's result does not depend on the batch it arrives in.  Pad channels have
    * k = v = 0 and stay exact zeros.  udp_hrnet_flops_per_image counts 2 C HW (the weighted sum) for it. */
-  UDP_OP_LINATTN = 16
+  UDP_OP_LINATTN = 16,
+  /* nn.LayerNorm(d), eps 1e-5, per token -- the norms of MobileViT's pre-norm TransformerEncoder and the one that closes
+   * a MobileViTBlock's global_rep (deep_hrnet/lib/models/backbones/mobilevit.py:112-113, :480-488, :566-568).  The
+   * reference applies it to the unfolded [B P, N, d] tensor (:593-632); a token is a pixel, so on the NHWC map it
+   * is a reduction over one pixel's contiguous channels and the map is never rearranged.  UDP_F32 and UDP_F16X2
+   * (UDP_BF16: UDP_ERR_UNSUPPORTED).  cin == cout == cout_pad = C, a multiple of 32 up to 512; chain_cout = r, the real
+   * channels (1 <= r <= C; the first r of the view) -- the field carries a count as it does for kind 15, no chained
+   * conv; hout == hin, wout == win, any size >= 1.  in_coff / in_pitch / out_coff / out_pitch are honoured (multiples
+   * of 8).  relu must be 0; no addends, second outputs, group, wfmt.  `out` MAY be `in` (same buffer, same view): a
+   * pixel's row sits in registers before its first store and every element is read and written by one thread.
+   * Parameter block at w_off (udp_conv2d_fused: `weights`; `bias` may be NULL), fp32 in EVERY storage mode: gamma [C],
+   * beta [C], zeros at the pad channels.  Per pixel:
+   *   mean = (1 / r) sum_c in[c]     var = (1 / r) sum_c (in[c] - mean)^2     (two-pass, never E[x^2] - E[x]^2)
+   *   out[c] = fmaf((in[c] - mean) * rstd, gamma[c], beta[c]),  rstd = 1 / sqrt(var + 1e-5)      for c < r
+   *     (mean and the subtraction in fp64, the difference and rstd rounded to fp32, the rest in fp32)
+   *   out[c] = 0                                                                                 for r <= c < C
+   * 16 lanes share a pixel: lane l adds the real channels of its 16-byte groups l, l + 16, ... in ascending order in
+   * fp64, then a butterfly over the 16 lanes.  The order depends on (C, r) only, nothing is atomic: an image's result
+   * does not depend on the batch it arrives in.  Not counted in udp_hrnet_flops_per_image. */
+  UDP_OP_LNORM = 17,
+  /* Soft-max multi-head self-attention for 2x2 patches: MultiHeadAttention.forward_other between qkv_proj and out_proj
+   * (backbones/mobilevit.py:436-457), with MobileViTBlock.unfolding / folding (:593-655) folded into indexing: pixel
+   * (y, x) of the NHWC map is position p = 2 (y & 1) + (x & 1) of patch (y / 2, x / 2), and the reference's [B P, N, d]
+   * token tensor means that attention mixes only the N = HW / 4 pixels of one position class of one image, in patch
+   * raster order.  UDP_F32 and UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED).  ks = 2 carries the patch size (anything
+   * else: UDP_ERR_ARG).  cout == cout_pad = dp, a multiple of 32 up to 256; cin = 3 dp: the output of the qkv conv as
+   * the planner stores it (through the conv's output-channel map) -- q real channels at [0, d), k at [dp, dp + d), v at
+   * [2 dp, 2 dp + d), zeros in the pads.  chain_cout = d, the real width (1 <= d <= dp; a count, no chained conv).
+   * up_shift[0] = the head count (with n_up == 0 the field is free for this kind): d % heads == 0 and head width
+   * hd = d / heads <= 64, else UDP_ERR_ARG.  Head h owns the REAL channels [h hd, (h + 1) hd) of q, k and v: padding
+   * never moves a head boundary.  hin == hout, win == wout, both even (odd sizes: UDP_ERR_ARG; the reference resizes such
+   * maps bilinearly, :598-605).  Views are honoured (multiples of 8); `out` must not be `in`.  relu must be 0; no
+   * weights / bias (may be NULL), addends, second outputs, group, wfmt.  The hd^-0.5 scaling of q (:441) is NOT applied:
+   * the planner folds it into the q rows of qkv_proj's weight and bias (in fp64, before packing).  Per image, class p,
+   * head h, over the class's N pixels:
+   *   s_ij = q_i . k_j        m_i = max_j s_ij        out_i = sum_j exp(s_ij - m_i) v_j / sum_j exp(s_ij - m_i)
+   * All fp32; UDP_F16X2 operands are decoded hi + lo * 2^-11 first and the result is split again on store, with the
+   * udp_f16x2_overflow range guard.  One thread per query row; the keys are walked in blocks of 32 staged in LDS (any N
+   * runs on the one code path), 8 keys per soft-max update: s_ij by fmaf over the head's channels in ascending order
+   * from 0; m' = max(m, max of the 8); l and the accumulator are multiplied by exp(m - m'); then for j ascending
+   * e = exp(s_ij - m'), l += e, acc = fmaf(e, v_j, acc); out = acc / l.  Keys past N are skipped.  For N <= 64 / 128 a
+   * workgroup runs 4 / 2 (class, head) pairs, a whole number of waves each.  The order depends on (N, hd) only, nothing
+   * is atomic: an image's result does not depend on the batch it arrives in.  Pad channels of the output are written
+   * as exact zeros.  udp_hrnet_flops_per_image counts 2 d N MACs per pixel (q k^T and the weighted sum). */
+  UDP_OP_MHATTN = 18,
+  /* out = act(in) element-wise, act = `relu` = UDP_ACT_SILU or UDP_ACT_HSWISH (0 and 1: UDP_ERR_ARG, as every code
+   * outside 0..4 and code 3; a ReLU rides in its producer's epilogue).  The two full 3x3 convs of a MobileViTBlock
+   * (backbones/mobilevit.py:531-534, :546-549) are followed by SiLU, and the 3x3 conv kernels have no SiLU epilogue:
+   * they run with code 0 and one of these follows.  UDP_F32 and UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED).
+   * cin == cout == cout_pad = C, a multiple of 32; hout == hin, wout == win, any size >= 1; views honoured (multiples
+   * of 8); `out` MAY be `in` (same buffer, same view): every element is read and written by one thread.  No weights /
+   * bias (may be NULL), addends, second outputs, chain, group, wfmt.  The arithmetic is that of the activation codes
+   * below, fp32; act(0) = 0, so zero pad channels stay exact zeros.  Not counted in udp_hrnet_flops_per_image. */
+  UDP_OP_ACT = 19
 };
 
 /* udp_conv_op.relu is an activation code.  UDP_ACT_HSWISH: v * (clamp(v + 3, 0, 6) / 6) in fp32, applied where the
@@ -209,7 +262,7 @@ enum udp_op_kind {
 
 typedef struct udp_conv_op {
   int32_t kind;            /* enum udp_op_kind */
-  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7; pad = ks/2; UDP_OP_LINATTN: 2 = the patch size), stride 1|2 */
+  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7; pad = ks/2; UDP_OP_LINATTN / UDP_OP_MHATTN: 2 = the patch size), stride 1|2 */
   int32_t relu;            /* activation of the epilogue: UDP_ACT_NONE / UDP_ACT_RELU / UDP_ACT_HSWISH / UDP_ACT_SILU (see there) */
   int32_t cin, cout;       /* real channel counts (cin multiple of 16 for UDP_OP_CONV) */
   int32_t cout_pad;        /* cout rounded up to a multiple of 32: rows of `weights`/`bias` */
@@ -302,9 +355,10 @@ double udp_hrnet_flops_per_image(const udp_hrnet* h);
 
 /* One fused conv launch on raw pointers (the operator the program above is made of; used by
  * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE,
- * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM or UDP_OP_LINATTN: NHWC in / out, weights as documented there, no res / up -- except the
+ * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM, UDP_OP_LINATTN, UDP_OP_LNORM, UDP_OP_MHATTN or UDP_OP_ACT: NHWC in / out, weights as documented there, no res / up -- except the
  * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`; UDP_OP_SE / UDP_OP_GNORM: `weights` = the parameter block, chain_cout = hidden width / real channels;
- * UDP_OP_LINATTN: no weights), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
+ * UDP_OP_LNORM: `weights` = the parameter block, chain_cout = real channels; UDP_OP_MHATTN: no weights, chain_cout = real width, up_shift[0] = heads;
+ * UDP_OP_LINATTN / UDP_OP_ACT: no weights), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
  * its buffer ids and blob offsets are ignored except out_buf == UDP_BUF_OUTPUT, which selects
  * the NCHW fp32 output form.  in/res/ups/out: NHWC `dtype`; weights [ks*ks][cout_pad][cin]
  * `dtype`; bias fp32 [cout_pad].  Replaces conv+BN(+add)(+ReLU), pose_hrnet.py:43-59.

@@ -4,7 +4,7 @@ per-op-class kernel time of udp_hrnet_profile (hipEvents around every launch, ea
 the achieved bytes/s on its algorithmic traffic (one read and one write of the map) next to the launch time of a
 UDP_OP_FUSE (an existing kernel that moves the same bytes) on a tensor of the same size, in the same session.
 
-    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32] [--model v2|plus|mobilevitv2]
+    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32] [--model v2|plus|mobilevitv2|mobilevit]
 
 ``--model plus``: pose_shufflenetv2_plus_pixel_shuffle (Small) instead, with the same measurements; its depthwise
 launches are classed by kernel size, and the squeeze-excitation launches and the 1x1 convs with the hard-swish
@@ -14,6 +14,10 @@ epilogue get classes of their own.
 with the SiLU epilogue and those with a residual get classes of their own, and a UDP_OP_GNORM and a UDP_OP_LINATTN
 launch on the layer-3 map (32 x 24, 64 channels; the attention reads the 160-channel qkv map) are timed against a
 UDP_OP_FUSE launch on the map they read.
+
+``--model mobilevit``: pose_mobilevit_pixel_shuffle (MODEL_SIZE xxs) instead; layer norm, multi-head attention, the
+stand-alone activation launches, the 1x1 convs by epilogue and the 3x3 convs get classes of their own (no side
+measurement).
 """
 import argparse
 import ctypes as C
@@ -40,6 +44,8 @@ PLUS_NAME = "pose_shufflenetv2_plus_pixel_shuffle"
 PLUS_EXTRA = dict(EXTRA, MODEL_SIZE="Small")
 MVIT_NAME = "pose_mobilevitv2_pixel_shuffle"
 MVIT_EXTRA = dict(EXTRA, MODEL_SIZE=0.5)
+VIT_NAME = "pose_mobilevit_pixel_shuffle"
+VIT_EXTRA = dict(EXTRA, MODEL_SIZE="xxs")
 
 
 def op_class(name, kind, ks, stride):
@@ -77,6 +83,12 @@ def op_class_mvit(op):
     if op["kind"] == _lib.UDP_OP_CONV and op["ks"] == 1 and op["name"] != "final_layer":
         return "conv1x1_silu" if op["relu"] == _lib.UDP_ACT_SILU else "conv1x1_res" if op["res"] is not None else "conv1x1"
     return op_class(op["name"], op["kind"], op["ks"], op["stride"])
+
+
+def op_class_vit(op):
+    """Classes of the MobileViT program: layer norm, multi-head attention, the activation launches, else as MobileViTv2."""
+    cls = {_lib.UDP_OP_LNORM: "lnorm", _lib.UDP_OP_MHATTN: "mhattn", _lib.UDP_OP_ACT: "act"}.get(op["kind"])
+    return cls or op_class_mvit(op)
 
 
 def _window(fn, reps):
@@ -162,10 +174,14 @@ def attn_vs_fuse(dtype, images, c=64, h=32, w=24):
             "us_min_max": [[round(lo * 1e3, 2), round(hi * 1e3, 2)] for _, lo, hi in t]}
 
 
-def run(dtype, n, steps, warmup, plus=False, mvit=False):
-    name = MVIT_NAME if mvit else PLUS_NAME if plus else NAME
-    cfg = {"MODEL": {"NAME": name, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian", "EXTRA": MVIT_EXTRA if mvit else PLUS_EXTRA if plus else EXTRA}}
-    if mvit:
+def run(dtype, n, steps, warmup, plus=False, mvit=False, vit=False):
+    name = VIT_NAME if vit else MVIT_NAME if mvit else PLUS_NAME if plus else NAME
+    cfg = {"MODEL": {"NAME": name, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian",
+                     "EXTRA": VIT_EXTRA if vit else MVIT_EXTRA if mvit else PLUS_EXTRA if plus else EXTRA}}
+    if vit:
+        from udp_pose_amd.synth_mobilevit import synth_mobilevit_state_dict
+        sd = synth_mobilevit_state_dict(seed=7)
+    elif mvit:
         from udp_pose_amd.synth_mobilevitv2 import synth_mobilevitv2_state_dict
         sd = synth_mobilevitv2_state_dict(seed=7)
     elif plus:
@@ -190,7 +206,7 @@ def run(dtype, n, steps, warmup, plus=False, mvit=False):
     ms_op, desc = net.profile(x, flip_test=True)           # second run: warm caches, kernels loaded
     classes = {}
     for k, ((name, kind, ks, stride, cin, cout, hout, wout), t) in enumerate(zip(desc, ms_op)):
-        cls = op_class_mvit(prog._ops[k]) if mvit else op_class_plus(prog._ops[k]) if plus else op_class(name, kind, ks, stride)
+        cls = op_class_vit(prog._ops[k]) if vit else op_class_mvit(prog._ops[k]) if mvit else op_class_plus(prog._ops[k]) if plus else op_class(name, kind, ks, stride)
         e = classes.setdefault(cls, {"launches": 0, "ms": 0.0})
         e["launches"] += 1
         e["ms"] += float(t)
@@ -198,7 +214,7 @@ def run(dtype, n, steps, warmup, plus=False, mvit=False):
     for e in classes.values():
         e["share"] = round(e["ms"] / total, 4)
         e["ms"] = round(e["ms"], 4)
-    side = {"attn_vs_fuse": attn_vs_fuse(dtype, 2 * n)} if mvit else {"dwconv_vs_fuse": dw_vs_fuse(dtype, 2 * n)}
+    side = {} if vit else {"attn_vs_fuse": attn_vs_fuse(dtype, 2 * n)} if mvit else {"dwconv_vs_fuse": dw_vs_fuse(dtype, 2 * n)}
     return {"dtype": dtype, "images_per_s": round(n / ms * 1000.0, 1), "ms_per_step": round(ms, 3),
             "ms_per_step_min_max": [round(ms_lo, 3), round(ms_hi, 3)], "windows": "5 windows of %d steps, median" % steps,
             "launches_per_forward": int(lib.udp_hrnet_num_launches(handle)),
@@ -212,11 +228,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--dtypes", default="f16x2,f32")
-    ap.add_argument("--model", choices=("v2", "plus", "mobilevitv2"), default="v2")
+    ap.add_argument("--model", choices=("v2", "plus", "mobilevitv2", "mobilevit"), default="v2")
     a = ap.parse_args()
-    plus, mvit = a.model == "plus", a.model == "mobilevitv2"
-    res = [run(d, a.batch, a.steps, a.warmup, plus, mvit) for d in a.dtypes.split(",")]
-    workload = ("pose_mobilevitv2_pixel_shuffle 0.5" if mvit else "pose_shufflenetv2_plus_pixel_shuffle Small" if plus
+    plus, mvit, vit = a.model == "plus", a.model == "mobilevitv2", a.model == "mobilevit"
+    res = [run(d, a.batch, a.steps, a.warmup, plus, mvit, vit) for d in a.dtypes.split(",")]
+    workload = ("pose_mobilevit_pixel_shuffle xxs" if vit else "pose_mobilevitv2_pixel_shuffle 0.5" if mvit else "pose_shufflenetv2_plus_pixel_shuffle Small" if plus
                 else "pose_shufflenetv2_10x_pixel_shuffle 1.0x")
     out = {"workload": workload + " 256x192 flip-test + DARK decode", "batch": a.batch, "results": res}
     if len(res) == 2:

@@ -148,6 +148,14 @@ int gnorm_validate(const udp_conv_op& o, int dtype);
 int linattn_validate(const udp_conv_op& o, int dtype);
 int describe_gnorm(ConvParams p, int dtype, Launch* out);
 int describe_linattn(ConvParams p, int dtype, Launch* out);
+// attn.hip: LayerNorm per pixel (UDP_OP_LNORM), soft-max multi-head self-attention (UDP_OP_MHATTN) and the stand-alone
+// activation (UDP_OP_ACT) of MobileViT
+int lnorm_validate(const udp_conv_op& o, int dtype);
+int mhattn_validate(const udp_conv_op& o, int dtype);
+int act_op_validate(const udp_conv_op& o, int dtype);
+int describe_lnorm(ConvParams p, int dtype, Launch* out);
+int describe_mhattn(ConvParams p, int dtype, Launch* out);
+int describe_act(ConvParams p, int dtype, Launch* out);
 int attn_h2_overflow(hipStream_t s, int reset, int* flag);
 int conv_h2_overflow(hipStream_t s, int reset, int* flag);       // conv.hip / conv_ws.hip / psa.hip: their g_h2_overflow
 int conv_ws_h2_overflow(hipStream_t s, int reset, int* flag);

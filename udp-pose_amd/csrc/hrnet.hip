@@ -62,7 +62,7 @@ static size_t esize(int dtype) { return dtype == UDP_BF16 ? 2 : 4; }   // bytes 
 static int act_validate(const udp_conv_op& o, int dtype, bool has_res) {
   if (o.relu < UDP_ACT_NONE || o.relu > UDP_ACT_SILU || o.relu == 3)
     return fail(UDP_ERR_ARG, "activation code %d (0 none, 1 ReLU, 2 hard-swish, 4 SiLU)", o.relu);
-  if (o.relu < UDP_ACT_HSWISH) return UDP_OK;
+  if (o.relu < UDP_ACT_HSWISH || o.kind == UDP_OP_ACT) return UDP_OK;      // (UDP_OP_ACT: act_op_validate has its rules)
   if (o.relu == UDP_ACT_SILU && o.kind == UDP_OP_DWCONV) return UDP_OK;      // (dwconv_validate refuses bf16)
   const bool plain1x1 = o.kind == UDP_OP_CONV && o.ks == 1 && o.stride == 1 && !o.group && !o.chain_cout && !o.n_up && !o.n_out2 && !has_res &&
                         !o.in_stuff2 && o.out_buf != UDP_BUF_OUTPUT;
@@ -77,7 +77,7 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
   const int nb = (int)h->buf_elems.size();
   auto buf_ok = [&](int b, int64_t need) { return b >= 0 && b < nb && h->buf_elems[b] >= need; };
   const int64_t out_need = (int64_t)o.hout * o.wout * (o.out_pitch ? o.out_pitch : o.cout);
-  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_LINATTN) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_ACT) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
   if (const int rc = act_validate(o, h->dtype, o.res_buf != UDP_BUF_NONE)) return rc;
   if (o.lane < 0 || o.lane >= UDP_MAX_LANES || o.n_wait < 0 || o.n_wait > UDP_MAX_WAIT) return fail(UDP_ERR_ARG, "op %d: lane/n_wait", idx);
   for (int k = 0; k < o.n_wait; ++k)
@@ -142,6 +142,21 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
       return fail(UDP_ERR_ARG, "op %d: %s", idx, gn ? "group norm in place needs the same view for in and out" : "linear attention: out must not be in");
     if (gn && (o.w_off < 0 || (size_t)o.w_off + (size_t)2 * o.cin * 4 > h->weights_bytes || (o.w_off & 15)))
       return fail(UDP_ERR_ARG, "op %d: group norm parameter block outside the blob or misaligned", idx);
+    return UDP_OK;
+  }
+  if (o.kind == UDP_OP_LNORM || o.kind == UDP_OP_MHATTN || o.kind == UDP_OP_ACT) {
+    // LayerNorm per pixel / soft-max multi-head attention / the stand-alone activation (attn.hip); the norm's and the
+    // activation's `out` may be the very view `in` is
+    const char* what = o.kind == UDP_OP_LNORM ? "layer norm" : o.kind == UDP_OP_MHATTN ? "multi-head attention" : "activation op";
+    const int rc = o.kind == UDP_OP_LNORM ? lnorm_validate(o, h->dtype) : o.kind == UDP_OP_MHATTN ? mhattn_validate(o, h->dtype) : act_op_validate(o, h->dtype);
+    if (rc) return rc;
+    const int ipitch = o.in_pitch ? o.in_pitch : o.cin;
+    if (!buf_ok(o.in_buf, (int64_t)o.hin * o.win * ipitch) || !buf_ok(o.out_buf, out_need) || o.res_buf != UDP_BUF_NONE)
+      return fail(UDP_ERR_ARG, "op %d: %s buffers missing or too small (or a residual)", idx, what);
+    if (o.in_buf == o.out_buf && (o.kind == UDP_OP_MHATTN || o.in_coff != o.out_coff || ipitch != (o.out_pitch ? o.out_pitch : o.cout)))
+      return fail(UDP_ERR_ARG, "op %d: %s: %s", idx, what, o.kind == UDP_OP_MHATTN ? "out must not be in" : "in place needs the same view for in and out");
+    if (o.kind == UDP_OP_LNORM && (o.w_off < 0 || (size_t)o.w_off + (size_t)2 * o.cin * 4 > h->weights_bytes || (o.w_off & 15)))
+      return fail(UDP_ERR_ARG, "op %d: layer norm parameter block outside the blob or misaligned", idx);
     return UDP_OK;
   }
   if (o.kind == UDP_OP_DWCONV || o.kind == UDP_OP_PIXSHUF) {
@@ -326,6 +341,8 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
     if (ops[i].kind == UDP_OP_DWCONV) h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cout * ops[i].hout * ops[i].wout;   // ks * ks MACs per output element
     if (ops[i].kind == UDP_OP_SE) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // the two small products (pool and scale are not counted)
     if (ops[i].kind == UDP_OP_LINATTN) h->flops += 2.0 * ops[i].cout * ops[i].hout * ops[i].wout;   // the weighted sum of the keys (soft-max and gate are not counted)
+    if (ops[i].kind == UDP_OP_MHATTN)      // q k^T and the weighted sum of the values: 2 d N MACs per pixel, N = HW / 4 keys
+      h->flops += 2.0 * 2 * ops[i].chain_cout * (ops[i].hout * ops[i].wout / 4) * ops[i].hout * ops[i].wout;
     if (ops[i].kind == UDP_OP_CONV && ops[i].chain_cout) h->flops += 2.0 * ops[i].cout * ops[i].chain_cout * ops[i].hout * ops[i].wout;
     h->ops.push_back(ops[i]);
   }
@@ -449,9 +466,13 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       p.up_shift[2] = o.chain_relu;
     }
     if (o.kind == UDP_OP_DWCONV) p.up_shift[0] = o.chain_cout;   // passthrough: real channels per half (n_up == 0)
-    if (o.kind == UDP_OP_SE || o.kind == UDP_OP_GNORM) {
+    if (o.kind == UDP_OP_SE || o.kind == UDP_OP_GNORM || o.kind == UDP_OP_LNORM) {
       p.wgt = h->weights + o.w_off;
       p.up_shift[0] = o.chain_cout;                              // hidden width / real channels
+    }
+    if (o.kind == UDP_OP_MHATTN) {
+      p.up_shift[0] = o.chain_cout;                              // real width d
+      p.up_shift[1] = o.up_shift[0];                             // heads (mhattn_validate: n_up == 0)
     }
     if (o.kind == UDP_OP_BLOCK) {
       p.wgt = h->weights + o.w_off;
@@ -479,6 +500,9 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
       case UDP_OP_SE: rc = describe_se(p, h->dtype, &ls[i]); break;
       case UDP_OP_GNORM: rc = describe_gnorm(p, h->dtype, &ls[i]); break;
       case UDP_OP_LINATTN: rc = describe_linattn(p, h->dtype, &ls[i]); break;
+      case UDP_OP_LNORM: rc = describe_lnorm(p, h->dtype, &ls[i]); break;
+      case UDP_OP_MHATTN: rc = describe_mhattn(p, h->dtype, &ls[i]); break;
+      case UDP_OP_ACT: rc = describe_act(p, h->dtype, &ls[i]); break;
       case UDP_OP_PIXSHUF: rc = describe_pixshuf(p, h->dtype, &ls[i]); break;
       default:
         if (o.chain_cout) {
@@ -815,10 +839,11 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (dtype != UDP_F32 && dtype != UDP_BF16 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "udp_conv2d_fused: dtype %d", dtype);
   if (n <= 0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: n=%d", n);
   if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV && o->kind != UDP_OP_DWCONV && o->kind != UDP_OP_PIXSHUF &&
-      o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LINATTN)
+      o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_LNORM && o->kind != UDP_OP_MHATTN &&
+      o->kind != UDP_OP_ACT)
     return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
   if (const int rc = act_validate(*o, dtype, res != nullptr)) return rc;
-  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && o->kind != UDP_OP_LINATTN && (!weights || (!bias && o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_MHATTN && o->kind != UDP_OP_ACT && (!weights || (!bias && o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LNORM))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
   if (o->kind == UDP_OP_SE) {
     const int rc = se_validate(*o, dtype);
     if (rc) return rc;
@@ -833,6 +858,14 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
     if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: %s takes no residual", gn ? "group norm" : "linear attention");
     if (in == out && (!gn || o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
       return fail(UDP_ERR_ARG, "udp_conv2d_fused: %s", gn ? "group norm in place needs the same view for in and out" : "linear attention: out must not be in");
+  }
+  if (o->kind == UDP_OP_LNORM || o->kind == UDP_OP_MHATTN || o->kind == UDP_OP_ACT) {
+    const char* what = o->kind == UDP_OP_LNORM ? "layer norm" : o->kind == UDP_OP_MHATTN ? "multi-head attention" : "activation op";
+    const int rc = o->kind == UDP_OP_LNORM ? lnorm_validate(*o, dtype) : o->kind == UDP_OP_MHATTN ? mhattn_validate(*o, dtype) : act_op_validate(*o, dtype);
+    if (rc) return rc;
+    if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: %s takes no residual", what);
+    if (in == out && (o->kind == UDP_OP_MHATTN || o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
+      return fail(UDP_ERR_ARG, "udp_conv2d_fused: %s: %s", what, o->kind == UDP_OP_MHATTN ? "out must not be in" : "in place needs the same view for in and out");
   }
   if (o->kind == UDP_OP_DWCONV || o->kind == UDP_OP_PIXSHUF) {
     const bool dw = o->kind == UDP_OP_DWCONV;
@@ -866,8 +899,11 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   p.Cout = o->cout;
   p.CoutPad = o->cout_pad;
   p.relu = o->relu;
-  if (o->kind == UDP_OP_SE || o->kind == UDP_OP_GNORM) {
-    p.up_shift[0] = o->chain_cout;      // hidden width / real channels (se_validate, gnorm_validate: n_up == 0, n_out2 == 0)
+  if (o->kind == UDP_OP_SE || o->kind == UDP_OP_GNORM || o->kind == UDP_OP_LNORM) {
+    p.up_shift[0] = o->chain_cout;      // hidden width / real channels (se_validate, gnorm_validate, lnorm_validate: n_up == 0, n_out2 == 0)
+  } else if (o->kind == UDP_OP_MHATTN) {
+    p.up_shift[0] = o->chain_cout;      // real width d
+    p.up_shift[1] = o->up_shift[0];     // heads (mhattn_validate: n_up == 0, n_out2 == 0)
   } else if (o->kind == UDP_OP_DWCONV) {
     if (o->n_out2) {
       p.nout2 = 1;
@@ -923,6 +959,9 @@ static int conv2d_fused_impl(const udp_conv_op* o, int dtype, int n, const void*
                  : o->kind == UDP_OP_SE     ? describe_se(p, dtype, &l)
                  : o->kind == UDP_OP_GNORM  ? describe_gnorm(p, dtype, &l)
                  : o->kind == UDP_OP_LINATTN ? describe_linattn(p, dtype, &l)
+                 : o->kind == UDP_OP_LNORM  ? describe_lnorm(p, dtype, &l)
+                 : o->kind == UDP_OP_MHATTN ? describe_mhattn(p, dtype, &l)
+                 : o->kind == UDP_OP_ACT    ? describe_act(p, dtype, &l)
                  : o->kind == UDP_OP_PIXSHUF ? describe_pixshuf(p, dtype, &l)
                                             : describe_conv(p, dtype, o->ks, o->stride, &l);
   if (rc) return rc;

@@ -511,7 +511,51 @@ def get_pose_net_mobilevitv2(cfg, is_train, **kwargs):
     return PoseMobileViTv2Hip(cfg, **kwargs)
 
 
+class PoseMobileViTHip(PoseNetHip):
+    """pose_mobilevit_pixel_shuffle (deep_hrnet/lib/models/pose_mobilevit_pixel_shuffle.py:23-60: the MobileViT xxs / xs /
+    s backbone -- MobileNetV2 blocks with SiLU, per-token LayerNorm and four-head soft-max self-attention on 2x2
+    patches, fused with the local features by a 3x3 conv --, the pixel-shuffle (DUC) decoder, ``final_layer``) inference
+    through the same C ABI; ``state_dict`` in the reference module's key format (``backbone.classifier`` is accepted and
+    unused, as in the reference's forward).  The width comes from MODEL.EXTRA.MODEL_SIZE; MODEL.CONFIG (the reference's
+    second YAML) is accepted and ignored.  Storage modes "f32" and "f16x2"; input height and width must be multiples
+    of 64."""
+
+    NAME = "pose_mobilevit_pixel_shuffle"
+    DTYPES = ("f32", "f16x2")
+
+    def __init__(self, cfg, dtype="f32"):
+        from .mobilevit_plan import mobilevit_spec
+        if dtype not in self.DTYPES:
+            raise NotImplementedError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
+        super().__init__(cfg, dtype)
+        self.extra = _get(cfg, "MODEL", "EXTRA")
+        self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
+        self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
+        self.spec = mobilevit_spec(self.extra, self.num_joints, self.target_type)   # NotImplementedError for an unknown size ...
+
+    def param_shapes(self):
+        from .synth_mobilevit import mobilevit_param_shapes
+        sp = self.spec
+        return mobilevit_param_shapes(model_size=sp["model_size"], num_joints=self.num_joints, target_type=self.target_type,
+                                      start_channels=sp["start_channels"], architecture=sp["architecture"],
+                                      final_kernel=sp["final_kernel"])
+
+    def init_weights(self, pretrained=""):
+        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+
+    def _make_program(self, h, w):
+        from .mobilevit_plan import MobileViTProgram
+        return MobileViTProgram(self._sd, self.spec, h, w, self.dtype)
+
+
+def get_pose_net_mobilevit(cfg, is_train, **kwargs):
+    """pose_mobilevit_pixel_shuffle.py:63-72 (``get_pose_net``); inference only -- the weights come from
+    ``load_state_dict``."""
+    return PoseMobileViTHip(cfg, **kwargs)
+
+
 MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet,
           "pose_shufflenetv2_10x_pixel_shuffle": get_pose_net_shufflenetv2,
           "pose_shufflenetv2_plus_pixel_shuffle": get_pose_net_shufflenetv2_plus,
-          "pose_mobilevitv2_pixel_shuffle": get_pose_net_mobilevitv2}
+          "pose_mobilevitv2_pixel_shuffle": get_pose_net_mobilevitv2,
+          "pose_mobilevit_pixel_shuffle": get_pose_net_mobilevit}

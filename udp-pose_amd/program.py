@@ -158,7 +158,7 @@ class Program:
                   w_off=0, b_off=0, w2_off=0, b2_off=0, group=0, wfmt=0, wexp=0,
                   in_coff=0, in_pitch=0, out_coff=0, out_pitch=0, res_coff=0, res_pitch=0, res_c=None,
                   chain_out=None, chain_cout=0, chain_relu=0, chain_wexp=0, chain_name=None,
-                  out2=[], add2=[], no_out=False)
+                  out2=[], add2=[], no_out=False, heads=0)
         unknown = set(fields) - set(op)
         if unknown:
             raise TypeError("%s: unknown op fields %s" % (name, sorted(unknown)))
@@ -354,6 +354,8 @@ class Program:
             o.n_up = len(op["ups"])
             for u, (t, s) in enumerate(op["ups"]):
                 o.up_buf[u], o.up_shift[u] = self._phys[t.id], s
+            if op["heads"]:
+                o.up_shift[0] = op["heads"]      # UDP_OP_MHATTN: the head count (n_up == 0 leaves the field free)
         return arr
 
     def weight_blob(self):

@@ -74,10 +74,12 @@ class ShuffleNetV2Program(Program):
 
     # ------------------------------------------------------------------ op helpers
     def _pw(self, name, x, w, b, relu, in_map=None, cin_t=None, out_map=None, cout_t=None, in_view=None, into=None,
-            to_output=False, res=None):
+            to_output=False, res=None, res_view=None):
         """One dense conv (1x1 / 3x3, stride 1) from an already folded weight, with the channel maps of ``_pack``.
         ``in_view = cin``: read the first ``cin`` channels of a wider ``x``; ``into = (tensor, coff)``; ``res``: a tensor
-        of the output's shape added in the epilogue (the MobileViTv2 planner's residuals)."""
+        of the output's shape added in the epilogue (the MobileViTv2 planner's residuals); ``res_view = (tensor, coff)``:
+        the residual is the output's width of channels from ``coff`` of a wider tensor (the MobileViT planner's shortcut
+        from the stem)."""
         ks = int(w.shape[2])
         head_ws = to_output and os.environ.get("UDP_POSE_HEAD_WS", "1") != "0"
         ws = self.use_ws and (not to_output or head_ws)
@@ -98,6 +100,11 @@ class ShuffleNetV2Program(Program):
             if (res.c, res.h, res.w) != (cout, x.h, x.w):
                 raise ValueError("%s: residual does not match the output" % name)
             views.update(res=res)
+        if res_view is not None:
+            rt, rc = res_view
+            if res is not None or (rt.h, rt.w) != (x.h, x.w) or rc + cout > rt.c:
+                raise ValueError("%s: residual view does not match the output" % name)
+            views.update(res=rt, res_coff=rc, res_pitch=rt.c, res_c=cout)
         self._emit(_lib.UDP_OP_CONV, name, x, out, ks=ks, stride=1, relu=relu, cin=cin, cout=cout, cout_pad=cout_pad,
                    hout=x.h, wout=x.w, w_off=w_off, b_off=b_off, wfmt=int(ws), wexp=wexp, **views)
         return out
