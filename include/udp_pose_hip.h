@@ -50,6 +50,9 @@ int udp_abi_version(void);
  * stored raises a device-side flag in the kernel that produced it -- at the source, because a NaN does not survive
  * the next ReLU and a finiteness test of the heat-maps can miss the event.  Waits for `stream`, then returns 1 if
  * any split-fp16 store since the last reset left the range, 0 if none, < 0 on error; reset != 0 clears the flag.
+ * The stems raise it for a pixel of the fp32 input image outside that range (or NaN) too: they split the image in
+ * registers, and what grows out of such a pixel is stored as 0 by their ReLU.  The flag is one per process, not per
+ * handle or stream: clear it before the forward whose verdict is wanted.
  * The caller re-runs such a batch in UDP_F32 (udp_pose_amd.pose_engine does; the reference engine is fp32,
  * deep_hrnet/pose_engine.py:99-127). */
 int udp_f16x2_overflow(void* stream, int reset);

@@ -690,6 +690,55 @@ def test_engine_reruns_a_batch_that_leaves_fp16_range_in_fp32(golden_dir):
     np.testing.assert_array_equal(kpf, kpf32)
 
 
+def test_engine_ignores_a_stale_range_flag(w32_gaussian):
+    """ADVICE (medium): the split-fp16 range flag is one per process.  A flag left behind by anything before the
+    engine's own forward (here a direct op call that stores 65520) must not cost an ordinary frame the fp32 re-run:
+    no retry is counted and the result equals a fresh engine's, bit for bit."""
+    import ctypes as C
+    from udp_pose_amd import _lib, f16x2
+    from udp_pose_amd.config import default_config
+    from udp_pose_amd.pose_engine import UdpPsaPoseHip
+    sd, _ = w32_gaussian
+    cfg = default_config()
+    cfg.MODEL.EXTRA = synth.W32_EXTRA
+    cfg.MODEL.IMAGE_SIZE = [192, 256]
+    cfg.MODEL.HEATMAP_SIZE = [48, 64]
+    cfg.DATASET.DATASET = "coco"
+    cfg.TEST.POST_PROCESS = True
+    frame = synth.synth_frame_u8(480, 640, seed=12)
+    boxes = synth.synth_boxes(3, seed=6)
+    fresh = UdpPsaPoseHip("synthetic", None, "cuda", state_dict=sd, config=cfg)
+    _lib.f16x2_overflow(reset=True)
+    kp0, mv0 = fresh.infer_pose(frame, boxes)
+    assert fresh.fp32_retries == 0
+
+    def raise_flag():                                               # 1x1 conv, zero weights, bias 65520 -> every output leaves the range
+        op = _lib.ConvOp()
+        op.kind, op.ks, op.stride, op.relu = _lib.UDP_OP_CONV, 1, 1, 0
+        op.cin, op.cout, op.cout_pad = 32, 32, 32
+        op.hin, op.win, op.hout, op.wout = 2, 2, 2, 2
+        x = f16x2.encode(torch.zeros(1, 2, 2, 32)).cuda()
+        w = f16x2.encode(torch.zeros(1, 32, 32)).cuda()
+        b = torch.full((32,), 65520.0).cuda()
+        out = f16x2.encode(torch.zeros(1, 2, 2, 32)).cuda()
+        _lib.check(_lib.lib().udp_conv2d_fused(C.byref(op), _lib.DTYPES["f16x2"], 1, _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), None, None, None,
+                                               None, _lib.ptr(out), _lib.stream_ptr()))
+        torch.cuda.synchronize()
+    eng = UdpPsaPoseHip("synthetic", None, "cuda", state_dict=sd, config=cfg)
+    for flip in (False, True):
+        raise_flag()
+        assert _lib.f16x2_overflow(reset=False), "the direct op call did not raise the flag: the test would be vacuous"
+        kp, mv = eng.infer_pose(frame, boxes, flip_test=flip)
+        assert eng.fp32_retries == 0, "a stale flag cost an ordinary frame the fp32 re-run"
+        assert not _lib.f16x2_overflow(reset=True)
+        if not flip:
+            np.testing.assert_array_equal(kp, kp0)
+            np.testing.assert_array_equal(mv, mv0)
+    kpf, mvf = fresh.infer_pose(frame, boxes, flip_test=True)
+    np.testing.assert_array_equal(kp, kpf)
+    np.testing.assert_array_equal(mv, mvf)
+
+
 def _batch_properties(net, x, n_img_check):
     """Size-independent properties at a config's own batch: graph replay == eager launches, identical crops ->
     identical maps, an image's maps do not depend on the batch it rides in, the in-kernel mirrored half == an

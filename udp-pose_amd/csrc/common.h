@@ -36,11 +36,19 @@ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 // Split-fp16 ("f16x2") range guard.  fp16 tops out at 65504: a value of magnitude >= 65520 splits into hi = inf, and
 // the NaN that grows out of it downstream does not survive a ReLU (max(NaN, 0) = 0), so a finiteness test of the
 // final heat-maps can miss it.  Every kernel that WRITES split-fp16 values therefore raises this flag at the source
-// (one per translation unit; udp_f16x2_overflow() ORs them).  m = the largest magnitude about to be split (NaN
-// compares false, so `!(m < limit)` catches it too).
+// (one per translation unit; udp_f16x2_overflow() ORs them).
+//   h2_range_check(m): m = the magnitude of ONE value about to be split (NaN compares false, so `!(m < limit)` catches
+//   it too).  Never hand it an fmaxf() over several values: fmaxf(NaN, x) = x loses a NaN among finite siblings.
+//   h2_range_check_bits(m): m = the largest h2_mag() of SEVERAL values.  The bit pattern of |v| as an unsigned integer
+//   orders like the magnitude, with inf and every NaN above all finite values, so an integer max keeps what fmaxf drops.
 static __device__ int g_h2_overflow;
 __device__ __forceinline__ void h2_range_check(float m) {
   if (!(m < 65520.f)) g_h2_overflow = 1;
+}
+__device__ __forceinline__ unsigned h2_mag(float v) { return __builtin_bit_cast(unsigned, v) & 0x7FFFFFFFu; }
+__device__ __forceinline__ unsigned h2_max(unsigned a, unsigned b) { return a > b ? a : b; }
+__device__ __forceinline__ void h2_range_check_bits(unsigned m) {
+  if (m >= __builtin_bit_cast(unsigned, 65520.f)) g_h2_overflow = 1;
 }
 // flag of the calling translation unit after `s` has drained; cleared when `reset`
 static inline int h2_overflow_fetch(hipStream_t s, int reset, int* flag) {

@@ -848,6 +848,7 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const ConvParams p) {
   float acc[16];
 #pragma unroll
   for (int q = 0; q < 16; ++q) acc[q] = b_s[cg * 16 + q];
+  unsigned in_mag = 0;
 #pragma unroll 1
   for (int tap = 0; tap < 9; ++tap) {   // rolled on purpose: a full unroll needs > 256 VGPRs
     const int ky = tap / 3, kx = tap - ky * 3;
@@ -859,6 +860,7 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const ConvParams p) {
 #pragma unroll
     for (int ci = 0; ci < 3; ++ci) {
       const float v = ok ? in[((size_t)ci * p.Hin + gy) * p.Win + sx] : 0.f;
+      if constexpr (std::is_same<T, H2>::value) in_mag = h2_max(in_mag, h2_mag(v));
 #pragma unroll
       for (int q = 0; q < 16; q += 4) {
         const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + ci * 64 + q);
@@ -869,6 +871,8 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const ConvParams p) {
       }
     }
   }
+  // split fp16: the same verdict on the image as stem_mfma_k, which splits it (a NaN pixel would be stored as 0 by the ReLU)
+  if constexpr (std::is_same<T, H2>::value) h2_range_check_bits(in_mag);
 #pragma unroll
   for (int q = 0; q < 16; q += 4) {
     f32x4 v = {acc[q], acc[q + 1], acc[q + 2], acc[q + 3]};
@@ -1029,6 +1033,7 @@ __global__ __launch_bounds__(256) void stem_mfma_k(const ConvParams p) {
     for (int nb = 0; nb < 4; ++nb) acc[nb] = bias[nb];
 #pragma unroll
     for (int nb = 0; nb < (SPLIT ? 4 : 1); ++nb) accx[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    unsigned in_mag = 0;               // SPLIT: the largest |input| of the lane's window (the image is split here too)
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
       Frag hi, lo;
@@ -1039,6 +1044,7 @@ __global__ __launch_bounds__(256) void stem_mfma_k(const ConvParams p) {
         const bool ok = ko != 0xFFFFu && gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win;
         const int sx = mirror ? p.Win - 1 - gx : gx;
         const float v = ok ? in[(size_t)(ko >> 8) * plane + (size_t)gy * p.Win + sx] : 0.f;
+        if constexpr (SPLIT) in_mag = h2_max(in_mag, h2_mag(v));
         hi[j] = (E)v;
         lo[j] = (E)((v - (float)hi[j]) * (SPLIT ? kLoScale : 1.f));
       }
@@ -1057,6 +1063,9 @@ __global__ __launch_bounds__(256) void stem_mfma_k(const ConvParams p) {
       }
     }
     if constexpr (SPLIT) {
+      // an input pixel outside fp16's range (or NaN) turns into inf - inf = NaN in the products, and the ReLU below
+      // stores that as 0: flag it here, where it is split
+      h2_range_check_bits(in_mag);
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) acc[nb] += accx[nb] * kLoInv;
     }
@@ -1153,6 +1162,7 @@ __global__ __launch_bounds__(256, 4) void stem7_conv_kernel(const ConvParams p) 
   float acc[16];
 #pragma unroll
   for (int q = 0; q < 16; ++q) acc[q] = w7_s[147 * 64 + cg * 16 + q];
+  unsigned in_mag = 0;
 #pragma unroll 1
   for (int tap = 0; tap < 49; ++tap) {
     const int ky = tap / 7, kx = tap - ky * 7;
@@ -1164,6 +1174,7 @@ __global__ __launch_bounds__(256, 4) void stem7_conv_kernel(const ConvParams p) 
 #pragma unroll
     for (int ci = 0; ci < 3; ++ci) {
       const float v = ok ? in[((size_t)ci * p.Hin + gy) * p.Win + sx] : 0.f;
+      if constexpr (std::is_same<T, H2>::value) in_mag = h2_max(in_mag, h2_mag(v));
 #pragma unroll
       for (int q = 0; q < 16; q += 4) {
         const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + ci * 64 + q);
@@ -1174,6 +1185,8 @@ __global__ __launch_bounds__(256, 4) void stem7_conv_kernel(const ConvParams p) 
       }
     }
   }
+  // split fp16: the same verdict on the image as stem7_lds_kernel, which splits it (a NaN pixel would be stored as 0 by the ReLU)
+  if constexpr (std::is_same<T, H2>::value) h2_range_check_bits(in_mag);
 #pragma unroll
   for (int q = 0; q < 16; q += 4) {
     f32x4 v = {acc[q], acc[q + 1], acc[q + 2], acc[q + 3]};
@@ -1798,6 +1811,12 @@ __global__ __launch_bounds__(256) void stem7_lds_kernel(const ConvParams p) {
         const int iy = rem / WC, ix = rem - iy * WC;
         win[(ch * WR + iy) * WP + ix] = v[i];
       }
+    }
+    if constexpr (SPLIT) {             // the image is split in registers below: an input pixel outside fp16's range (or
+      unsigned m = 0;                  // NaN) would reach the store as a NaN that the ReLU turns into 0
+#pragma unroll
+      for (int i = 0; i < PER; ++i) m = h2_max(m, h2_mag(v[i]));
+      h2_range_check_bits(m);
     }
   };
   const int r = wave >> 1, xl = (wave & 1) * 16 + li;          // the lane's output pixel inside the tile

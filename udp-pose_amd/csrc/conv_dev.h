@@ -157,8 +157,7 @@ __device__ __forceinline__ void st4(void* base, size_t pix, int pitch, int c, f3
   } else {
     _Float16* q = reinterpret_cast<_Float16*>(base) + pix * (2 * (size_t)pitch) + c;
     f16x4 hi, lo;
-    h2_range_check(__builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])),
-                                   __builtin_fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3]))));
+    h2_range_check_bits(h2_max(h2_max(h2_mag(v[0]), h2_mag(v[1])), h2_max(h2_mag(v[2]), h2_mag(v[3]))));
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       hi[k] = (_Float16)v[k];
@@ -171,9 +170,8 @@ __device__ __forceinline__ void st4(void* base, size_t pix, int pitch, int c, f3
 
 // split / join of the H2 form for 8 consecutive channels held as two accumulator quads
 __device__ __forceinline__ void h2_split8(const f32x4& a, const f32x4& b, f16x8& hi, f16x8& lo) {
-  h2_range_check(__builtin_fmaxf(
-      __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a[0]), __builtin_fabsf(a[1])), __builtin_fmaxf(__builtin_fabsf(a[2]), __builtin_fabsf(a[3]))),
-      __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(b[0]), __builtin_fabsf(b[1])), __builtin_fmaxf(__builtin_fabsf(b[2]), __builtin_fabsf(b[3])))));
+  h2_range_check_bits(h2_max(h2_max(h2_max(h2_mag(a[0]), h2_mag(a[1])), h2_max(h2_mag(a[2]), h2_mag(a[3]))),
+                             h2_max(h2_max(h2_mag(b[0]), h2_mag(b[1])), h2_max(h2_mag(b[2]), h2_mag(b[3])))));
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     hi[q] = (_Float16)a[q];

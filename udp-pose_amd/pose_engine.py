@@ -171,6 +171,10 @@ class UdpPsaPoseHip:
         pose_input, cs = self._preprocess(img, boxes)
         n = cs.shape[0]
         offset = self.config.MODEL.TARGET_TYPE == "offset"
+        if self.model.dtype == "f16x2":
+            # the range flag is one per process: whatever an earlier raw_forward, model call or direct op call left
+            # in it says nothing about this batch
+            _lib.f16x2_overflow(reset=True)
         hm = self._heatmaps(self.model, pose_input, n, flip_test, offset)
         if self.model.dtype == "f16x2" and _lib.f16x2_overflow(reset=True):
             # split-fp16 storage has fp16's range (|x| < 65520).  The kernels flag a value that leaves it where it is

@@ -63,6 +63,8 @@ def encode_weights(wp, dtype):
     if dtype == "bf16":
         return wp.to(torch.bfloat16).contiguous().view(torch.uint8).numpy().tobytes()
     if dtype == "f16x2":
+        if not bool(torch.isfinite(wp).all()):                  # (a NaN compares False with every bound below)
+            raise ValueError("f16x2 storage: non-finite weight")
         if wp.numel() and float(wp.abs().max()) >= 32768.0:
             raise ValueError("f16x2 storage: a BatchNorm-folded weight of magnitude %g exceeds the fp16 range"
                              % float(wp.abs().max()))
