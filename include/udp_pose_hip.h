@@ -81,7 +81,10 @@ enum udp_op_kind {
   UDP_OP_STEM7 = 3,   /* 7x7 s2 p3 conv, Cin=3, reads the NCHW fp32 network input (RSN top) */
   UDP_OP_MAXPOOL = 4, /* MaxPool2d(3, stride 2, pad 1) */
   UDP_OP_BILINEAR = 5, /* bilinear resize, align_corners=True, hin x win -> hout x wout */
-  /* Polarized self-attention PSA_s (deep_hrnet/lib/models/PSA.py:190-269) of pose_hrnet_psa, per image;
+  /* Polarized self-attention PSA_s (deep_hrnet/lib/models/PSA.py:190-269) of pose_hrnet_psa and pose_resnet_psa, per
+   * image.  C divides 256 and is a multiple of 16, or C = 512 (layer 4 of ResNet-18 / 34: a separate set of kernels with
+   * the wave's lanes along the channels / along the weight rows); any other C is UDP_ERR_UNSUPPORTED at the first
+   * forward.  Accepting 512 added no symbol and no field: UDP_POSE_ABI_VERSION stays as it is.
    * w_off = fp32 block wq[C] | Wv[C/2][C] | W1[C/8][C/2] | b1 | ln_g | ln_b | W2[C][C/8] | b2[C] | Wg[C/2][C] */
   UDP_OP_PSA_POOL = 6,  /* in = x [C];   out = fp32 {sum_p softmax(wq.x)_p x_p, mean_p x_p}  (2C floats) */
   UDP_OP_PSA_MLP = 7,   /* in = POOL out; out = fp32 {channel mask m[C], gbar[C/2]}            (3C/2 floats) */
@@ -636,7 +639,7 @@ int udp_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t coun
  * see, so UDP_POSE_ABI_VERSION stays as it is.
  *
  * One block, per image on an NHWC map x [h*w][c] of `dtype` (UDP_F32 | UDP_BF16; c divides 256, a multiple of 16,
- * at least 32):
+ * at least 32 -- the inference ops UDP_OP_PSA_* also take c = 512, training does not):
  *   a = softmax_HW(wq.x_p)   xbar = sum_p a_p x_p   m = sigmoid(W2 relu(LN(W1 Wv xbar + b1)) + b2)   x1 = x * m[c]
  *   gbar = Wg mean_p(x1)     theta = Wt x1          s_p = sigmoid(sum_j gbar_j softmax_HW(theta_j)_p) x2 = x1 * s_p
  * theta (c/2 channels) and its backward (dWt, dx1 += Wt^T dtheta) are the caller's 1x1 conv: udp_conv2d_fused,

@@ -17,8 +17,6 @@ emits one ``udp_conv_op`` (include/udp_pose_hip.h) per fused launch:
 """
 import os
 
-import torch
-
 from . import _lib
 from .program import BN_EPS, DTYPES, Program, _T, _V, _round_up, encode_weights, storage_bytes  # noqa: F401 (re-exported)
 
@@ -59,32 +57,6 @@ class HRNetProgram(Program):
         out = self._new(32, x.h, x.w)
         self._emit(_lib.UDP_OP_BLOCK, q + ".block", x, out, ks=3, relu=1, w_off=w1, b_off=b1, w2_off=w2, b2_off=b2)
         return out
-
-    def _psa(self, x, p):
-        """PSA_s (PSA.py:190-269) as POOL -> MLP -> SCALE -> 1x1 conv (theta) -> SP; see csrc/psa.hip."""
-        sd, C = self.sd, x.c
-        if 256 % C or C % 16:
-            raise ValueError("%s: PSA needs a channel count that divides 256 (got %d)" % (p, C))
-        f32 = lambda k: sd[p + k].detach().to(torch.float32).cpu().reshape(-1)
-        block = torch.cat([f32(".conv_q_right.weight"), f32(".conv_v_right.weight"), f32(".conv_up.0.weight"),
-                           f32(".conv_up.0.bias"), f32(".conv_up.1.weight"), f32(".conv_up.1.bias"),
-                           f32(".conv_up.3.weight"), f32(".conv_up.3.bias"), f32(".conv_q_left.weight")])
-        want = C + C // 2 * C + C // 8 * (C // 2) + 3 * (C // 8) + C * (C // 8) + C + C // 2 * C
-        if block.numel() != want:
-            raise ValueError("%s: PSA parameter shapes do not match planes=%d" % (p, C))
-        w_off = self._put(block.numpy().tobytes())
-        f = 4 // storage_bytes(self.dtype)                               # fp32 side rows, counted in dtype elements
-        geom = dict(cin=C, cout=C, hin=x.h, win=x.w, hout=x.h, wout=x.w, w_off=w_off)       # of the attended map, whatever the operand
-        pooled = self._new(2 * C * f, 1, 1)
-        self._emit(_lib.UDP_OP_PSA_POOL, p + ".pool", x, pooled, **geom)
-        mask = self._new((C + C // 2) * f, 1, 1)
-        self._emit(_lib.UDP_OP_PSA_MLP, p + ".mlp", pooled, mask, **geom)
-        x1 = self._new(C, x.h, x.w)
-        self._emit(_lib.UDP_OP_PSA_SCALE, p + ".scale", x, x1, res=mask, **geom)
-        theta = self._conv(x1, p + ".conv_v_left", None, relu=False)
-        x2 = self._new(C, x.h, x.w)
-        self._emit(_lib.UDP_OP_PSA_SP, p + ".sp", theta, x2, res=x1, ups=[(mask, 0)], **dict(geom, cin=C // 2))
-        return x2
 
     def _build(self):
         sd = self.sd

@@ -359,13 +359,17 @@ class PoseResNetHip(PoseNetHip):
     DTYPES = ("f32", "f16x2")
 
     def __init__(self, cfg, dtype="f32"):
-        from .resnet_plan import pose_resnet_spec
         if dtype not in self.DTYPES:
-            raise ValueError("pose_resnet: dtype %r is not supported; supported modes: %s" % (dtype, ", ".join(self.DTYPES)))
+            raise ValueError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
         super().__init__(cfg, dtype)
         self.extra = _get(cfg, "MODEL", "EXTRA")
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
-        self.spec = pose_resnet_spec(self.extra)          # NotImplementedError for depths / kernels without a kernel
+        self.spec = self._spec_of(self.extra)             # NotImplementedError for depths / kernels without a kernel
+
+    @staticmethod
+    def _spec_of(extra):
+        from .resnet_plan import pose_resnet_spec
+        return pose_resnet_spec(extra)
 
     def param_shapes(self):
         from .synth_resnet import pose_resnet_param_shapes
@@ -375,7 +379,7 @@ class PoseResNetHip(PoseNetHip):
                                         deconv_with_bias=sp["deconv_with_bias"])
 
     def init_weights(self, pretrained=""):
-        raise NotImplementedError("pose_resnet: training (and its weight initialisation) is out of scope; load a state_dict")
+        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
 
     def _make_program(self, h, w):
         from .resnet_plan import PoseResNetProgram
@@ -386,6 +390,38 @@ def get_pose_net_resnet(cfg, is_train, **kwargs):
     """pose_resnet.py:263-273 (``get_pose_net``): the model for MODEL.EXTRA.NUM_LAYERS; inference only -- the weights
     come from ``load_state_dict`` (training, hence ``init_weights`` under is_train, is out of scope)."""
     return PoseResNetHip(cfg, **kwargs)
+
+
+class PoseResNetPsaHip(PoseResNetHip):
+    """pose_resnet_psa (deep_hrnet/lib/models/pose_resnet_psa.py:105-273): NUM_LAYERS 18 / 34 are BasicBlock ResNets
+    with a polarized self-attention block (PSA_s, 64 to 512 channels) after bn1 of every block; 50 / 101 / 152 are the
+    reference's plain Bottleneck nets (only its BasicBlock carries the attention), the programs of ``PoseResNetHip``.
+    The same deconv head, ``final_layer``, storage modes and refusals."""
+
+    NAME = "pose_resnet_psa"
+
+    @staticmethod
+    def _spec_of(extra):
+        from .resnet_plan import pose_resnet_psa_spec
+        return pose_resnet_psa_spec(extra)
+
+    def param_shapes(self):
+        if not self.spec["basic"]:
+            return super().param_shapes()
+        from .synth_resnet import pose_resnet_psa_param_shapes
+        sp = self.spec
+        return pose_resnet_psa_param_shapes(layers=sp["layers"], num_joints=self.num_joints, deconv_filters=sp["deconv_filters"],
+                                            deconv_kernel=4, final_kernel=sp["final_kernel"],
+                                            deconv_with_bias=sp["deconv_with_bias"])
+
+    def _make_program(self, h, w):
+        from .resnet_plan import PoseResNetPsaProgram
+        return PoseResNetPsaProgram(self._sd, self.spec, h, w, self.dtype)
+
+
+def get_pose_net_resnet_psa(cfg, is_train, **kwargs):
+    """pose_resnet_psa.py:263-273 (``get_pose_net``); inference only -- the weights come from ``load_state_dict``."""
+    return PoseResNetPsaHip(cfg, **kwargs)
 
 
 class PoseShuffleNetV2Hip(PoseNetHip):
@@ -555,6 +591,7 @@ def get_pose_net_mobilevit(cfg, is_train, **kwargs):
 
 
 MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet,
+          "pose_resnet_psa": get_pose_net_resnet_psa,
           "pose_shufflenetv2_10x_pixel_shuffle": get_pose_net_shufflenetv2,
           "pose_shufflenetv2_plus_pixel_shuffle": get_pose_net_shufflenetv2_plus,
           "pose_mobilevitv2_pixel_shuffle": get_pose_net_mobilevitv2,

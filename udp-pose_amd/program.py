@@ -5,7 +5,8 @@ include/udp_pose_hip.h per fused launch), a packed weight blob and an activation
 
 The planners (hrnet_plan.HRNetProgram, rsn_plan.RSNProgram, resnet_plan.PoseResNetProgram) derive from it and
 supply ``_build()``: they walk their reference graph and call the one fold (``_fold``), the one packer (``_pack``)
-and the one op emitter (``_emit``) here.
+and the one op emitter (``_emit``) here; the polarized self-attention block (``_psa``) is here too, for the two nets
+that carry one (pose_hrnet_psa, pose_resnet_psa).
 
 * BatchNorm(eval) is folded into the conv: w' = w * gamma/sqrt(var+eps),
   b' = beta - mean*gamma/sqrt(var+eps), computed in fp64, stored fp32 / bf16.
@@ -243,6 +244,32 @@ class Program:
                    hout=ho, wout=wo, res=res, ups=list(ups), w_off=w_off, b_off=b_off, group=group, wfmt=int(ws), wexp=wexp,
                    **views)
         return (out, z) if chain is not None else out
+
+    def _psa(self, x, p):
+        """PSA_s (PSA.py:190-269) as POOL -> MLP -> SCALE -> 1x1 conv (theta) -> SP; see csrc/psa.hip."""
+        sd, C = self.sd, x.c
+        if (256 % C or C % 16) and C != 512:
+            raise ValueError("%s: PSA needs a channel count that divides 256, or 512 (got %d)" % (p, C))
+        f32 = lambda k: sd[p + k].detach().to(torch.float32).cpu().reshape(-1)
+        block = torch.cat([f32(".conv_q_right.weight"), f32(".conv_v_right.weight"), f32(".conv_up.0.weight"),
+                           f32(".conv_up.0.bias"), f32(".conv_up.1.weight"), f32(".conv_up.1.bias"),
+                           f32(".conv_up.3.weight"), f32(".conv_up.3.bias"), f32(".conv_q_left.weight")])
+        want = C + C // 2 * C + C // 8 * (C // 2) + 3 * (C // 8) + C * (C // 8) + C + C // 2 * C
+        if block.numel() != want:
+            raise ValueError("%s: PSA parameter shapes do not match planes=%d" % (p, C))
+        w_off = self._put(block.numpy().tobytes())
+        f = 4 // storage_bytes(self.dtype)                               # fp32 side rows, counted in dtype elements
+        geom = dict(cin=C, cout=C, hin=x.h, win=x.w, hout=x.h, wout=x.w, w_off=w_off)       # of the attended map, whatever the operand
+        pooled = self._new(2 * C * f, 1, 1)
+        self._emit(_lib.UDP_OP_PSA_POOL, p + ".pool", x, pooled, **geom)
+        mask = self._new((C + C // 2) * f, 1, 1)
+        self._emit(_lib.UDP_OP_PSA_MLP, p + ".mlp", pooled, mask, **geom)
+        x1 = self._new(C, x.h, x.w)
+        self._emit(_lib.UDP_OP_PSA_SCALE, p + ".scale", x, x1, res=mask, **geom)
+        theta = self._conv(x1, p + ".conv_v_left", None, relu=False)
+        x2 = self._new(C, x.h, x.w)
+        self._emit(_lib.UDP_OP_PSA_SP, p + ".sp", theta, x2, res=x1, ups=[(mask, 0)], **dict(geom, cin=C // 2))
+        return x2
 
     # ------------------------------------------------------------------ lanes + buffers
     @staticmethod
