@@ -530,6 +530,19 @@ typedef struct udp_wgrad_item {
  * (member, tile, cout block) is computed exactly once. */
 int udp_debug_multi_order(const unsigned* tiles, const unsigned* ncby, const int* code, int n, unsigned cap,
                           unsigned* out_member, unsigned* out_tile, unsigned* out_cby, int* used_table);
+/* Diagnostic, host only (no GPU, no HIP call): the tile and kernel arm the library's choosers pick for one UDP_OP_CONV
+ * without channel views -- ks 1 | 3, stride 1 | 2, batch n, output map hout x wout, cin -> cout channels, nchw_out = the
+ * net's NCHW fp32 output, grouped = as a member of a launch group.  wfmt 1 (UDP_F16X2): the weight-stationary chooser,
+ * out[0] = PB (pixel blocks per wave of the instantiation that runs), out[1] = CP (cout pairs per workgroup).  wfmt 0:
+ * the LDS-staged chooser, out[0] = NB (16-channel cout blocks per workgroup), out[1] = MBW (pixel blocks per wave).
+ * Then out[2..7] = G, R, TW (tile = G images x R rows x TW columns), one stage buffer (0 | 1), dynamic LDS bytes,
+ * workgroups; out[8] = grid.x of the persistent bf16 form when that is what runs (every workgroup then strides over
+ * ceil(tiles / out[8]) tiles), else 0.  The choosers read UDP_POSE_WS_PB, UDP_POSE_WS_CP, UDP_POSE_MINWGS and
+ * UDP_POSE_MAXM at every call, so a test can force an arm around one call.  Returns UDP_OK, 1 when grouped is set and
+ * the conv is no member of a merged launch, or the error udp_conv2d_fused would return.  Adds a symbol only:
+ * UDP_POSE_ABI_VERSION stays as it is. */
+int udp_debug_conv_tile(int dtype, int wfmt, int ks, int stride, int n, int hout, int wout, int cin, int cout,
+                        int nchw_out, int grouped, int* out);
 int udp_conv2d_wgrad_group(const udp_wgrad_item* items, int n_items, int dtype, void* stream);
 /* Up to 4 independent plain convs (same dtype and batch n) in as few launches as possible -- the same-depth convs
  * of the HRNet branches in the training step (pose_hrnet.py:253-256): members whose tile fits the merged kernel run

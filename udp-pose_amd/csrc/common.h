@@ -135,6 +135,11 @@ struct Launch {
 };
 // conv_ws.hip: the weight-stationary split-fp16 convs (tile choice + kernel of one conv; merged launch of 2..4)
 int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped = false);
+struct WsTile {
+  int cp, pb, G, R, TW, wgs, sbuf;
+  size_t lds;
+};
+int choose_conv_ws(ConvParams& p, int ks, int stride, bool grouped, WsTile* best);   // its tile choice alone (host arithmetic, no HIP call)
 int describe_ws_multi(const Launch* members, int n, ConvMulti* m, Launch* out);
 int describe_conv_chain(ConvParams p, Launch* out);   // two 1x1 convs chained through registers (udp_conv_op.chain_cout)
 void ws_set_fill_wgs(long wgs);                       // workgroups a conv launched on its own should reach (tile choice)

@@ -1432,20 +1432,29 @@ static int describe_persist_mbw(const ConvParams& p, int mbw, size_t lds, int gr
 }
 
 // Persistent single-chunk form (bf16, Cin = 32): returns 1 when it does not apply.
-static int describe_persist(const ConvParams& p, int ks, int stride, int nb, int mbw, Launch* out) {
+// Its grid.x (workgroups per cout block, each striding over ceil(ntiles / grid.x) tiles) and LDS bytes; 0 when the form
+// does not apply.  Host arithmetic only (udp_debug_conv_tile reports it).
+static int persist_grid(const ConvParams& p, int ks, int stride, int nb, size_t* lds_out) {
   const int npix = p.G * p.IH * p.IW;
-  if (p.out_nchw_f32 || p.Cin != 32 || npix > MAXGP * 64 || p.ntiles >= 65536 || p.bn_ws || p.in_stuff2) return 1;
+  if (p.out_nchw_f32 || p.Cin != 32 || npix > MAXGP * 64 || p.ntiles >= 65536 || p.bn_ws || p.in_stuff2) return 0;
   if (p.in_pitch != p.Cin || p.in_coff || p.out_pitch != p.Cout || p.out_coff || (p.res && (p.res_pitch != p.Cout || p.res_coff)))
-    return 1;                                         // channel-slice views: generic kernel
+    return 0;                                         // channel-slice views: generic kernel
+  if (!((ks == 3 || ks == 1) && (stride == 1 || (stride == 2 && ks == 3)))) return 0;   // the UDP_CASE list of describe_persist
   const size_t lds = (size_t)(ks * ks * nb * 16 + 2 * ((npix + 15) / 16) * 16) * ROWB;
   int per_cu = (int)((150 * 1024) / lds);
   if (per_cu > 4) per_cu = 4;
-  if (per_cu < 1) return 1;
+  if (per_cu < 1) return 0;
   const int cblocks = p.CoutPad / (nb * 16);
   const int budget = ceil_div(256 * per_cu, cblocks);
-  if (p.ntiles < 2 * budget) return 1;               // one tile per workgroup: nothing to overlap
+  if (p.ntiles < 2 * budget) return 0;               // one tile per workgroup: nothing to overlap
   const int rounds = ceil_div(p.ntiles, budget);
-  const int grid_x = ceil_div(p.ntiles, rounds);
+  *lds_out = lds;
+  return ceil_div(p.ntiles, rounds);
+}
+static int describe_persist(const ConvParams& p, int ks, int stride, int nb, int mbw, Launch* out) {
+  size_t lds = 0;
+  const int grid_x = persist_grid(p, ks, stride, nb, &lds);
+  if (grid_x == 0) return 1;
 #define UDP_CASE(K, S, B) \
   if (ks == K && stride == S && nb == B) return describe_persist_mbw<K, S, B>(p, mbw, lds, grid_x, out);
   UDP_CASE(3, 1, 2) UDP_CASE(3, 1, 4) UDP_CASE(3, 2, 2) UDP_CASE(3, 2, 4) UDP_CASE(1, 1, 2) UDP_CASE(1, 1, 4)
@@ -1548,6 +1557,66 @@ int describe_conv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
   if (dtype == UDP_F32) return describe_conv_t<float>(p, ks, stride, nb, mbw, lds, out);
   if (dtype == UDP_F16X2) return describe_conv_t<H2>(p, ks, stride, nb, mbw, lds, out);
   return describe_conv_t<__bf16>(p, ks, stride, nb, mbw, lds, out);
+}
+
+// Diagnostic (tests/test_conv_arms_cpu.py, no GPU needed): the decision of the two tile choosers for one UDP_OP_CONV
+// without channel views, as describe_conv / describe_conv_grouped would take it -- choose_conv_ws for wfmt 1,
+// conv_choose_tile otherwise.  Host arithmetic only: no kernel is looked up and no HIP call is made.
+extern "C" int udp_debug_conv_tile(int dtype, int wfmt, int ks, int stride, int n, int hout, int wout, int cin, int cout,
+                                   int nchw_out, int grouped, int* out) {
+  if (!out || n < 1 || hout < 1 || wout < 1 || cin < 1 || cout < 1) return fail(UDP_ERR_ARG, "udp_debug_conv_tile: bad argument");
+  if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2)) return fail(UDP_ERR_ARG, "udp_debug_conv_tile: ks/stride");
+  if (dtype != UDP_F32 && dtype != UDP_BF16 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "udp_debug_conv_tile: dtype %d", dtype);
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.N = n;
+  p.Hout = hout;
+  p.Wout = wout;
+  p.Hin = hout * stride;
+  p.Win = wout * stride;
+  p.Cin = p.in_pitch = cin;
+  p.Cout = p.out_pitch = p.res_pitch = cout;
+  p.CoutPad = (cout + 31) / 32 * 32;
+  p.out_nchw_f32 = nchw_out ? 1 : 0;
+  p.wfmt = wfmt;
+  p.flip_from = n;
+  if (p.Cin % 16 != 0) return fail(UDP_ERR_UNSUPPORTED, "conv Cin=%d is not a multiple of 16", p.Cin);
+  if (!p.out_nchw_f32 && p.Cout % 16 != 0) return fail(UDP_ERR_UNSUPPORTED, "NHWC conv Cout=%d is not a multiple of 16", p.Cout);
+  for (int i = 0; i < 9; ++i) out[i] = 0;
+  if (wfmt == 1) {
+    if (dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "wfmt 1 (fragment-major weights) needs UDP_F16X2");
+    if (grouped && (stride != 1 || p.out_nchw_f32)) return 1;          // describe_conv_grouped: not a member of a merged launch
+    WsTile t{};
+    if (const int rc = choose_conv_ws(p, ks, stride, grouped != 0, &t)) return rc;
+    out[0] = t.pb;
+    out[1] = t.cp;
+    out[5] = t.sbuf;
+    out[6] = (int)t.lds;
+    out[7] = t.wgs;
+  } else {
+    if (wfmt != 0) return fail(UDP_ERR_ARG, "conv wfmt=%d", wfmt);
+    if (grouped && (dtype == UDP_F32 || stride != 1 || p.out_nchw_f32)) return 1;
+    int nb = 2;
+    const size_t lds = conv_choose_tile(p, ks, stride, dtype, &nb, grouped != 0);
+    if (p.CoutPad % (nb * 16) != 0) return fail(UDP_ERR_UNSUPPORTED, "conv CoutPad=%d is not a multiple of %d", p.CoutPad, nb * 16);
+    const int mbw = ceil_div(ceil_div(p.G * p.R * p.TW, 16), 4);
+    if (grouped && (nb != 2 || p.G * p.R * p.TW > 256)) return 1;
+    if (mbw < 1 || mbw > 4) return fail(UDP_ERR_UNSUPPORTED, "conv tile of %d pixel blocks per wave has no kernel", mbw);
+    out[0] = nb;
+    out[1] = mbw;
+    out[5] = p.sbuf;
+    out[6] = (int)lds;
+    out[7] = p.ntiles * (p.CoutPad / (nb * 16));
+    if (dtype == UDP_BF16 && !grouped && getenv("UDP_POSE_NO_PERSIST") == nullptr) {
+      size_t plds = 0;
+      out[8] = persist_grid(p, ks, stride, nb, &plds);
+      if (out[8]) out[6] = (int)plds;
+    }
+  }
+  out[2] = p.G;
+  out[3] = p.R;
+  out[4] = p.TW;
+  return UDP_OK;
 }
 
 // A conv that will share one launch with the same-depth convs of other branches (hrnet.hip merges them

@@ -617,10 +617,6 @@ static int describe_ws_hs(const ConvParams& p, int pb, int cp, size_t lds, Launc
 #undef UDP_WS
   return 1;
 }
-struct WsTile {
-  int cp, pb, G, R, TW, wgs, sbuf;
-  size_t lds;
-};
 // Tile of a (cout pairs per workgroup, pixel blocks per wave) candidate; false if it cannot be built.
 static bool ws_tile(const ConvParams& p, int ks, int stride, int cp, int pb, WsTile* t, bool own_launch) {
   const int pg = 4 / cp;
@@ -692,7 +688,10 @@ static bool ws_tile(const ConvParams& p, int ks, int stride, int cp, int pb, WsT
 static long g_ws_fill_wgs = 512;
 void ws_set_fill_wgs(long wgs) { g_ws_fill_wgs = wgs; }
 
-int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped) {
+// Tile choice of describe_conv_ws: fills the tile fields of `p` and `best` (cout pairs per workgroup, pixel blocks per
+// wave, LDS bytes, workgroups).  Host arithmetic only -- no HIP call -- so that udp_debug_conv_tile (conv.hip) can
+// report the decision without a GPU.
+int choose_conv_ws(ConvParams& p, int ks, int stride, bool grouped, WsTile* best_out) {
   if (p.relu >= UDP_ACT_HSWISH && (ks != 1 || stride != 1 || p.out_nchw_f32 || p.res || p.nup || p.nout2 || grouped))
     return fail(UDP_ERR_UNSUPPORTED, "hard-swish / SiLU (activation codes 2, 4): plain 1x1 stride-1 NHWC convs on their own launch only");
   if ((stride != 1 && stride != 2) || (ks != 3 && ks != 1) || (p.out_nchw_f32 && stride != 1))
@@ -747,6 +746,13 @@ int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped
   if (getenv("UDP_POSE_DEBUG_TILES"))
     fprintf(stderr, "ws conv k%d s%d %dx%d C%d->%d: G=%d R=%d TW=%d CP=%d PB=%d lds=%zu%s wgs=%d\n", ks, stride, p.Hout, p.Wout, p.Cin,
             p.Cout, p.G, p.R, p.TW, best.cp, best.pb, best.lds, best.sbuf ? " (one stage buffer)" : "", best.wgs);
+  *best_out = best;
+  return UDP_OK;
+}
+
+int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped) {
+  WsTile best{};
+  if (const int crc = choose_conv_ws(p, ks, stride, grouped, &best)) return crc;
   int rc = 1;
   if (best.pb == 8) {
     rc = describe_ws_pb8(p, best.lds, out);
