@@ -91,6 +91,8 @@ struct ConvParams {
   int wfmt;              // udp_conv_op.wfmt: 1 = fragment-major split-fp16 weights (conv_ws_h2_kernel)
   int wexp;              // udp_conv_op.wexp: those weights are stored scaled by 2^wexp
   int in_stuff2;         // udp_conv_op.in_stuff2: conv_mfma_kernel reads the [Hin/2][Win/2] input as its zero-stuffed image
+  int out_skip;          // NCHW fp32 output of the weight-stationary kernels: images >= flip_from are written out_skip image
+                         // rows further on (a sub-batch lane's mirrored half lands behind ALL the plain images, hrnet.hip)
   double* bn_ws;         // training: per-workgroup BatchNorm partial sums of the output, [tile][2*Cout] (or null)
   // udp_conv_op.n_out2: second outputs out2[k] = out (as stored) + add2[k] of the weight-stationary split-fp16 convs
   void* out2[2];
@@ -131,6 +133,7 @@ struct Launch {
   unsigned lds = 0;
   int groupable = 0;   // conv described by describe_conv_grouped: may be merged with its group siblings
   int ws_cp = 0;       // weight-stationary member: its cout pairs per workgroup
+  int pair = 0;        // this launch also does the NEXT op's work (describe_head_chain): the executor skips that op's own launch
   ConvParams p;
 };
 // conv_ws.hip: the weight-stationary split-fp16 convs (tile choice + kernel of one conv; merged launch of 2..4)
@@ -142,7 +145,9 @@ struct WsTile {
 int choose_conv_ws(ConvParams& p, int ks, int stride, bool grouped, WsTile* best);   // its tile choice alone (host arithmetic, no HIP call)
 int describe_ws_multi(const Launch* members, int n, ConvMulti* m, Launch* out);
 int describe_conv_chain(ConvParams p, Launch* out);   // two 1x1 convs chained through registers (udp_conv_op.chain_cout)
-void ws_set_fill_wgs(long wgs);                       // workgroups a conv launched on its own should reach (tile choice)
+// a 1x1 conv with up-sampled addends + ReLU chained into the 1x1 conv that writes the net's NCHW fp32 output; 1: no such kernel
+int describe_head_chain(ConvParams p, const ConvParams& p2, Launch* out);
+void ws_set_fill_wgs(long wgs);                      // workgroups a conv launched on its own should reach (tile choice)
 int ws_set_stamps(unsigned long long* dev_buf);      // diagnostic builds (-DUDP_STAMPS) only
 // deconv.hip: ConvTranspose2d(k=4, s=2, p=1) + folded BatchNorm (+ ReLU), UDP_OP_DECONV (fp32 and split fp16)
 int describe_deconv(ConvParams p, int dtype, Launch* out);

@@ -1541,6 +1541,8 @@ int describe_conv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
     return describe_conv_ws(p, ks, stride, out);
   }
   if (p.wfmt != 0) return fail(UDP_ERR_ARG, "conv wfmt=%d", p.wfmt);
+  // (only the weight-stationary kernels place a lane's mirrored half: never write those rows anywhere else)
+  if (p.out_skip) return fail(UDP_ERR_UNSUPPORTED, "conv: an output written in place for a sub-batch lane (out_skip) needs fragment-major weights (wfmt 1)");
   int nb = 2;
   const size_t lds = conv_choose_tile(p, ks, stride, dtype, &nb);
   if (p.CoutPad % (nb * 16) != 0)

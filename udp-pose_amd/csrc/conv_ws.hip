@@ -99,7 +99,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   constexpr bool dbg_nores = false;
 #endif
   const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(
-      p.out, 0, (!p.out || dbg_nost) ? 0 : NCHW ? out_pix * p.Cout * 4 : out_pix * outpb, 0x00020000);
+      p.out, 0, (!p.out || dbg_nost) ? 0 : NCHW ? (out_pix + (unsigned)p.out_skip * p.Hout * p.Wout) * p.Cout * 4 : out_pix * outpb, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_bias = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.bias), 0, (unsigned)p.CoutPad * 4u, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_res = __builtin_amdgcn_make_buffer_rsrc(
@@ -377,7 +377,8 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
       const int crd = ocrd[i];
       const int y = crd & 1023, xo = (crd >> 10) & 1023, n = crd >> 20;
       const unsigned hw = __umul24(p.Hout, p.Wout);
-      const unsigned base = __umul24(__umul24(__umul24(n, p.Cout), p.Hout) + y, p.Wout) + xo;
+      const int no = n >= p.flip_from ? n + p.out_skip : n;     // ConvParams::out_skip (0 everywhere but in a sub-batch lane)
+      const unsigned base = __umul24(__umul24(__umul24(no, p.Cout), p.Hout) + y, p.Wout) + xo;
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -1219,6 +1220,222 @@ int describe_conv_chain(ConvParams p, Launch* out) {
   out->groupable = 0;
   out->p = p;
   out->p.sbuf = getenv("UDP_POSE_CHAIN_DBG") ? atoi(getenv("UDP_POSE_CHAIN_DBG")) : 0;   // timing-only ablations (results WRONG): 1 no weights, 2 no stores, 4 no residual, 8 no X
+  return UDP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Chained head (hrnet.hip marks the pair; the last two ops of an HRNet-W32 program: stage4's last fuse conv and
+// final_layer, pose_hrnet.py:456-470):
+//     Y = ReLU(W . X + b + sum_u nearest_up(up_u))    Cin = 32  ->  Cout = 128        (NOT written: nothing else reads it)
+//     Z = W2 . Y_as_stored + b2                        128      ->  Cout2 <= 32 * Q    (NCHW fp32, the net's output)
+// On their own the two launches write the 128-channel map to HBM and read it straight back: 546 MB for 128 images
+// at 64x48, of which X, the addends and Z are 143 MB.  The technique is conv_chain_kernel's: a pixel-stationary wave
+// owns 16 * PB flat pixels, keeps their X fragments (one K chunk) and walks the NP = 4 cout pairs of the first conv;
+// the accumulators of pair p, after conv_ws_body's epilogue (fma(acc, 2^-wexp, bias), the addends u = 0, 1, 2, ReLU)
+// and the split into (hi, lo) -- with the range check of the store that no longer happens -- are the B fragment of K
+// chunk p of the second conv.  Every accumulator sees the MFMAs of the separate launches in their order (hi * Bhi,
+// lo * Bhi, hi * 2^-11 * Blo, chunk by chunk), so Z is theirs bit for bit.  (The separate launch also adds the empty
+// residual, + 0.0f, in front of the addends: that can only turn a -0 into a +0, which the ReLU does anyway.)
+// Both weight sets (16 KiB + Q * 16 KiB) and the biases live in LDS, staged once by a persistent 8-wave workgroup
+// (conv_chain_kernel's notes: streamed from L2 the fragments made it issue-bound).
+// Fields of the second conv ride in ConvParams members the first one does not use: wgt2 / bias2 = W2 / b2, out2[0] = Z,
+// out2_pitch[0] = Cout2, out2_coff[0] = wexp2; flip_from / out_skip place Z's image rows (a sub-batch lane's).
+template <int Q>
+__global__ __launch_bounds__(512) void conv_head_chain_kernel(const ConvParams p) {
+  constexpr int ESZ = 2, NB = 2, PB = 2, NP = 4, NWAVES = 8;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 15, kg = lane >> 4;
+  const unsigned hw = (unsigned)p.Hout * p.Wout;
+  const unsigned npix = (unsigned)p.N * hw;
+  const int cout2 = p.out2_pitch[0];
+  const unsigned inpb = (unsigned)p.in_pitch * ESZ * 2, in_lo = (unsigned)p.in_pitch * ESZ;
+  const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.in), 0, npix * inpb, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wgt), 0, (unsigned)NP * 4096u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wgt2), 0, (unsigned)NP * Q * 4096u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_z = __builtin_amdgcn_make_buffer_rsrc(p.out2[0], 0, (unsigned)(p.N + p.out_skip) * hw * (unsigned)cout2 * 4u, 0x00020000);
+  const float winv = __builtin_ldexpf(1.f, -p.wexp), winv2 = __builtin_ldexpf(1.f, -p.out2_coff[0]);
+  // addends: dense [N][Hout >> s][Wout >> s][Cout] split-fp16 maps (zero-length descriptor: no such addend)
+  const unsigned uppb = (unsigned)p.Cout * ESZ * 2, up_lo = (unsigned)p.Cout * ESZ;
+  __amdgpu_buffer_rsrc_t r_up[3];
+#pragma unroll
+  for (int u = 0; u < 3; ++u)
+    r_up[u] = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.up[u]), 0,
+                                                u < p.nup ? (unsigned)p.N * (p.Hout >> p.up_shift[u]) * (p.Wout >> p.up_shift[u]) * uppb : 0u, 0x00020000);
+
+  // ---- LDS: [W1: NP blocks of 4 KiB][W2: NP * Q blocks, (chunk, pair) order][b1: 128 floats][b2: 32 * Q floats]
+  constexpr unsigned kW2 = (unsigned)NP * 4096u, kBias = kW2 + (unsigned)NP * Q * 4096u;
+  for (unsigned off = threadIdx.x * 16u; off < kBias; off += 512u * 16u) {
+    const u32x4 v = off < kW2 ? __builtin_amdgcn_raw_buffer_load_b128(r_w, off, 0, 0) : __builtin_amdgcn_raw_buffer_load_b128(r_w2, off - kW2, 0, 0);
+    *reinterpret_cast<u32x4*>(smem + off) = v;
+  }
+  float* sbias = reinterpret_cast<float*>(smem + kBias);
+  if (threadIdx.x < 128 + 32 * Q) sbias[threadIdx.x] = threadIdx.x < 128 ? p.bias[threadIdx.x] : p.bias2[threadIdx.x - 128];
+  __syncthreads();
+  // A fragments of the 4 KiB block at `blk`: (nb, plane) at 2048 * nb + 1024 * plane, lane l's 8 K values at 16 * l
+  auto load_a = [&](unsigned blk, f16x8 (&h)[NB], f16x8 (&l)[NB]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      const unsigned char* q = smem + blk + (unsigned)lane * 16u + 2048u * nb;
+      h[nb] = *reinterpret_cast<const f16x8*>(q);
+      l[nb] = *reinterpret_cast<const f16x8*>(q + 1024);
+    }
+  };
+  auto mfma3 = [&](f32x4 (&acc)[NB], const f16x8 (&h)[NB], const f16x8 (&l)[NB], const f16x8 (&a2)[NB], const f16x8 bh, const f16x8 bl)
+      __attribute__((always_inline)) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h[nb], bh, acc[nb], 0, 0, 0);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(l[nb], bh, acc[nb], 0, 0, 0);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[nb], bl, acc[nb], 0, 0, 0);
+      };
+
+  const unsigned ngroups = (npix + PB * 16 - 1) / (PB * 16);
+  for (unsigned grp = (unsigned)blockIdx.x * NWAVES + wave; grp < ngroups; grp += gridDim.x * NWAVES) {
+    unsigned pix[PB], upoff[PB][3];
+    int pn[PB], py[PB], px[PB];
+    bool ok[PB];
+    f16x8 xh[PB], xl[PB];
+#pragma unroll
+    for (int i = 0; i < PB; ++i) {
+      pix[i] = grp * (PB * 16) + i * 16 + li;
+      ok[i] = pix[i] < npix;
+      const unsigned pc = ok[i] ? pix[i] : 0u;
+      pn[i] = (int)(pc / hw);
+      const unsigned rem = pc - (unsigned)pn[i] * hw;
+      py[i] = (int)(rem / (unsigned)p.Wout);
+      px[i] = (int)(rem - (unsigned)py[i] * p.Wout);
+      // X fragment: lane (kg, li) holds channels 8kg .. + 7 of pixel li (hi and lo planes); masked pixels read zeros
+      const unsigned off = ok[i] ? pix[i] * inpb + (unsigned)(p.in_coff + 8 * kg) * ESZ : kOobOff;
+      xh[i] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_in, off, 0, 0));
+      xl[i] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_in, off + in_lo, 0, 0));
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {     // nearest up-sampling: pixel (n, y >> s, x >> s) of addend u
+        const int sh = u < p.nup ? p.up_shift[u] : 0;
+        const unsigned up_pix = (unsigned)(pn[i] * (p.Hout >> sh) + (py[i] >> sh)) * (unsigned)(p.Wout >> sh) + (unsigned)(px[i] >> sh);
+        upoff[i][u] = ok[i] ? up_pix * uppb : kOobOff;
+      }
+    }
+    f32x4 acc2[PB][Q][NB];
+#pragma unroll
+    for (int i = 0; i < PB; ++i)
+#pragma unroll
+      for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc2[i][q][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // one cout pair of the first conv = one K chunk of the second (straight-line code, see conv_chain_kernel)
+#pragma unroll
+    for (int pr = 0; pr < NP; ++pr) {
+      // (the pairs are kept apart: left alone hipcc hoists the addend and fragment loads of all four -- 126 spilled registers)
+      __builtin_amdgcn_sched_barrier(0);
+      const int cbase = 32 * pr + 8 * kg;
+      // the pair's addends (8 consecutive channels of the up-sampled pixel, hi and lo), requested before its MFMAs;
+      // an absent addend reads zeros through its zero-length descriptor: no branch around loads
+      u32x4 uh[PB][3], ul[PB][3];
+#pragma unroll
+      for (int i = 0; i < PB; ++i)
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+          uh[i][u] = __builtin_amdgcn_raw_buffer_load_b128(r_up[u], upoff[i][u] + (unsigned)cbase * ESZ, 0, 0);
+          ul[i][u] = __builtin_amdgcn_raw_buffer_load_b128(r_up[u], upoff[i][u] + (unsigned)cbase * ESZ + up_lo, 0, 0);
+        }
+      f16x8 ah[NB], al[NB], a2[NB];
+      load_a((unsigned)pr * 4096u, ah, al);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) a2[nb] = ah[nb] * (_Float16)0x1p-11f;
+      f32x4 bias[NB];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) bias[nb] = *reinterpret_cast<const f32x4*>(smem + kBias + (unsigned)(cbase + 4 * nb) * 4u);
+      f16x8 yh[PB], yl[PB];
+#pragma unroll
+      for (int i = 0; i < PB; ++i) {
+        f32x4 acc[NB];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        mfma3(acc, ah, al, a2, xh[i], xl[i]);
+        // epilogue of the first conv for this pair: conv_ws_body's, value by value
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[nb][q] = __builtin_fmaf(acc[nb][q], winv, bias[nb][q]);
+#pragma unroll
+        for (int u = 0; u < 3; ++u) h2_add8(acc[0], acc[1], __builtin_bit_cast(f16x8, uh[i][u]), __builtin_bit_cast(f16x8, ul[i][u]));
+        if (p.relu) {
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[nb][q] = acc[nb][q] > 0.f ? acc[nb][q] : 0.f;
+        }
+        h2_split8(acc[0], acc[1], yh[i], yl[i]);
+      }
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        f16x8 bh[NB], bl[NB], b2[NB];
+        load_a(kW2 + (unsigned)(pr * Q + q) * 4096u, bh, bl);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) b2[nb] = bh[nb] * (_Float16)0x1p-11f;
+#pragma unroll
+        for (int i = 0; i < PB; ++i) mfma3(acc2[i][q], bh, bl, b2, yh[i], yl[i]);
+      }
+    }
+    // epilogue of the second conv: conv_ws_body's NCHW fp32 one (channels >= Cout2 are padding)
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      f32x4 b2[NB];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) b2[nb] = *reinterpret_cast<const f32x4*>(smem + kBias + 512u + (unsigned)(32 * q + 8 * kg + 4 * nb) * 4u);
+#pragma unroll
+      for (int i = 0; i < PB; ++i) {
+        const int no = pn[i] >= p.flip_from ? pn[i] + p.out_skip : pn[i];
+        const unsigned base = ((unsigned)no * (unsigned)cout2 * (unsigned)p.Hout + (unsigned)py[i]) * (unsigned)p.Wout + (unsigned)px[i];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int cc = 32 * q + 8 * kg + 4 * nb + k;
+            const float f = __builtin_fmaf(acc2[i][q][nb][k], winv2, b2[nb][k]);
+            const unsigned off = (ok[i] && cc < cout2) ? (base + (unsigned)cc * hw) * 4u : kOobOff;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, f), r_z, off, 0, 0);
+          }
+      }
+    }
+  }
+}
+
+// `p`: the first conv as describe_all resolved it; `p2`: the second one (UDP_BUF_OUTPUT writer).  Returns 1 when there
+// is no instantiation for the pair (the caller keeps the two launches).
+int describe_head_chain(ConvParams p, const ConvParams& p2, Launch* out) {
+  const int q = p2.CoutPad / 32;
+  if (p.Cin != 32 || p.Cout != 128 || p.CoutPad != 128 || p2.Cin != 128 || (q != 1 && q != 2) || p2.Cout > p2.CoutPad || p.wfmt != 1 ||
+      p2.wfmt != 1 || p.relu != UDP_ACT_RELU || p2.relu || p.res || p2.res || p2.nup || p.nout2 || p2.nout2 || !p2.out_nchw_f32 ||
+      p.Hin != p.Hout || p.Win != p.Wout || p2.Hout != p.Hout || p2.Wout != p.Wout || p2.N != p.N || p.in_pitch % 8 || p.in_coff % 8)
+    return 1;
+  const long npix = (long)p.N * p.Hout * p.Wout;
+  // 32-bit buffer offsets: X, the largest addend (shift 1: a quarter of the pixels, 128 channels) and Z
+  if (npix * p.in_pitch * 4 >= 0x7FFF0000L || npix * 128 >= 0x7FFF0000L || (long)(p.N + p2.out_skip) * p.Hout * p.Wout * p2.Cout * 4 >= 0x7FFF0000L) return 1;
+  for (int u = 0; u < p.nup; ++u)
+    if (!p.up[u]) return 1;
+  p.wgt2 = p2.wgt;
+  p.bias2 = p2.bias;
+  p.out2[0] = p2.out;
+  p.out2_pitch[0] = p2.Cout;
+  p.out2_coff[0] = p2.wexp;
+  p.flip_from = p2.flip_from;
+  p.out_skip = p2.out_skip;
+  p.out = nullptr;                       // Y is not written
+  const long groups = (npix + 31) / 32;
+  out->fn = q == 1 ? reinterpret_cast<const void*>(&conv_head_chain_kernel<1>) : reinterpret_cast<const void*>(&conv_head_chain_kernel<2>);
+  out->lds = (unsigned)(4 * 4096 + 4 * q * 4096 + (128 + 32 * q) * 4);
+  out->grid = dim3((unsigned)std::min<long>(256, (groups + 7) / 8));     // persistent: one 8-wave workgroup per CU (192 / 216 registers)
+  out->block = dim3(512);
+  out->groupable = 0;
+  out->ws_cp = 0;
+  out->p = p;
+  UDP_HIP_CHECK(hipFuncSetAttribute(out->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)out->lds));
+  if (getenv("UDP_POSE_DEBUG_TILES"))
+    fprintf(stderr, "head chain %dx%d C%d->%d->%d: wgs=%u lds=%u\n", p.Hout, p.Wout, p.Cin, p.Cout, p2.Cout, out->grid.x, out->lds);
   return UDP_OK;
 }
 

@@ -150,7 +150,9 @@ __device__ void write_preds(double cx, double cy, bool f32_coords, const double*
   }
 }
 
-// One workgroup per (image, joint) map.  LDS: raw map, row-pass, blurred map.
+// One workgroup per (image, joint) map.  LDS: raw map and row pass; the blurred map takes the raw map's place (the raw
+// map is dead after the row pass: its peak and arg-max are in registers) -- 2 * h * w * 4 bytes, 24 KiB for a 64x48
+// map, so that six workgroups share a CU and the 1088 maps of 64 crops x 17 joints run in one round instead of two.
 __global__ __launch_bounds__(256) void decode_gaussian_kernel(
     const float* __restrict__ hm, int j, int h, int w, const double* __restrict__ center,
     const double* __restrict__ scale, int cs_is_f32, int post, Taps t7, double* __restrict__ preds,
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(256) void decode_gaussian_kernel(
   const int hw = h * w;
   float* raw = sm;
   float* tmp = sm + hw;
-  float* blr = sm + 2 * hw;
+  float* blr = sm;       // written by the column pass only, behind the barrier that ends the row pass's reads of `raw`
   const int map = blockIdx.x;
   const int n = map / j;
   const float* src = hm + (size_t)map * hw;
@@ -328,11 +330,12 @@ static int make_taps(int ksize, Taps* t) {
   return udp_gaussian_taps_host(ksize, t->k);
 }
 
+// planes: h x w fp32 LDS buffers of the kernel (decode_gaussian_kernel 2, decode_offset_kernel 3)
 static int check_decode_args(const char* who, const void* hm, int n, int j, int h, int w, const void* c,
-                             const void* s, const void* preds, const void* maxvals, const void* pin) {
+                             const void* s, const void* preds, const void* maxvals, const void* pin, int planes) {
   if (!hm || !c || !s || !preds || !maxvals || !pin) return fail(UDP_ERR_ARG, "%s: null pointer", who);
   if (n < 0 || j <= 0 || h <= 0 || w <= 0) return fail(UDP_ERR_ARG, "%s: bad shape n=%d j=%d h=%d w=%d", who, n, j, h, w);
-  if ((size_t)h * w * 3 * sizeof(float) > 150 * 1024)
+  if ((size_t)h * w * planes * sizeof(float) > 150 * 1024)
     return fail(UDP_ERR_UNSUPPORTED, "%s: map %dx%d does not fit the LDS working set", who, h, w);
   return UDP_OK;
 }
@@ -340,12 +343,12 @@ static int check_decode_args(const char* who, const void* hm, int n, int j, int 
 extern "C" int udp_decode_gaussian(const float* heatmaps, int n, int j, int h, int w, const double* center,
                                    const double* scale, int cs_is_f32, int post_process, double* preds,
                                    float* maxvals, double* preds_in, int32_t* argidx, void* stream) {
-  int rc = check_decode_args("udp_decode_gaussian", heatmaps, n, j, h, w, center, scale, preds, maxvals, preds_in);
+  int rc = check_decode_args("udp_decode_gaussian", heatmaps, n, j, h, w, center, scale, preds, maxvals, preds_in, 2);
   if (rc) return rc;
   if (n == 0) return UDP_OK;
   Taps t7;
   make_taps(7, &t7);
-  const size_t lds = (size_t)h * w * 3 * sizeof(float);
+  const size_t lds = (size_t)h * w * 2 * sizeof(float);
   static bool attr = false;
   if (!attr) {
     UDP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_gaussian_kernel),
@@ -361,7 +364,7 @@ extern "C" int udp_decode_gaussian(const float* heatmaps, int n, int j, int h, i
 extern "C" int udp_decode_offset(const float* heatmaps, int n, int j, int h, int w, const double* center,
                                  const double* scale, int cs_is_f32, float kpd, double* preds, float* maxvals,
                                  double* preds_in, int32_t* argidx, void* stream) {
-  int rc = check_decode_args("udp_decode_offset", heatmaps, n, j, h, w, center, scale, preds, maxvals, preds_in);
+  int rc = check_decode_args("udp_decode_offset", heatmaps, n, j, h, w, center, scale, preds, maxvals, preds_in, 3);
   if (rc) return rc;
   if (n == 0) return UDP_OK;
   Taps t15, t7;

@@ -24,7 +24,7 @@ int run_launch(const Launch& l, hipStream_t s);
 using namespace udp;
 
 struct GraphEntry {
-  int n, flip;
+  int n, flip, skip;     // skip: ConvParams::out_skip of the output writers (a sub-batch lane writing its rows in place)
   const void* in;
   void* ws;
   void* out;
@@ -52,6 +52,9 @@ struct udp_hrnet {
   // sub-batch lanes (udp_hrnet_forward): the second half of a batch runs on this stream beside the first
   hipStream_t split_stream = nullptr;
   hipEvent_t split_fork = nullptr, split_join = nullptr;
+  // every writer of UDP_BUF_OUTPUT honours ConvParams::out_skip (decided once, at create): the lanes of a flip-test
+  // batch write their heat-map rows where the caller wants them; otherwise they are staged and copied into place
+  bool out_in_place = false;
 };
 
 static size_t esize(int dtype) { return dtype == UDP_BF16 ? 2 : 4; }   // bytes per stored element (F16X2: hi + lo)
@@ -351,6 +354,10 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
     delete h;
     return fail(UDP_ERR_ARG, "udp_hrnet_create: program needs a stem op first and the output op last, both on lane 0");
   }
+  // the weight-stationary split-fp16 kernels (fragment-major weights) are the output writers that place rows (out_skip)
+  h->out_in_place = dtype == UDP_F16X2;
+  for (int i = 0; i < n_ops; ++i)
+    if (ops[i].out_buf == UDP_BUF_OUTPUT && (ops[i].kind != UDP_OP_CONV || ops[i].wfmt != 1)) h->out_in_place = false;
   h->op_signals.assign(n_ops, 0);
   for (int i = 0; i < n_ops; ++i) {
     if (ops[i].lane + 1 > h->n_lanes) h->n_lanes = ops[i].lane + 1;
@@ -406,7 +413,46 @@ extern "C" int udp_hrnet_num_launches(const udp_hrnet* h) { return h ? (int)h->o
 extern "C" double udp_hrnet_flops_per_image(const udp_hrnet* h) { return h ? h->flops : 0.0; }
 
 // Resolves buffers / weights of every op for this call and picks kernels + tiles.
-static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, char* ws, float* out,
+// Chained head (conv_ws.hip, conv_head_chain_kernel): op i = a split-fp16 1x1 conv with ReLU (and up-sampled addends)
+// into a dense NHWC buffer that ONLY op i + 1 reads, op i + 1 = the plain 1x1 conv that writes the net's output.  Then
+// L[i] becomes the one launch of both and the buffer is never written.  UDP_POSE_NO_HEAD_CHAIN=1 keeps the two launches
+// (read per describe, so that handles created after a change see it); every program whose tail does not match --
+// W48, 16-channel branches, the LDS-staged head (wfmt 0), bf16 / fp32 -- keeps them too.
+static int mark_head_chain(const udp_hrnet* h, std::vector<Launch>& L) {
+  const char* off = getenv("UDP_POSE_NO_HEAD_CHAIN");
+  if (h->dtype != UDP_F16X2 || (off && atoi(off) != 0)) return UDP_OK;
+  for (size_t i = 0; i + 1 < h->ops.size(); ++i) {
+    const udp_conv_op& a = h->ops[i];
+    const udp_conv_op& b = h->ops[i + 1];
+    if (a.kind != UDP_OP_CONV || a.ks != 1 || a.stride != 1 || a.wfmt != 1 || a.relu != UDP_ACT_RELU || a.cin % 32 || a.out_buf < 0 ||
+        a.out_coff || (a.out_pitch && a.out_pitch != a.cout) || a.res_buf != UDP_BUF_NONE || a.n_out2 || a.chain_cout || a.group || a.in_stuff2)
+      continue;
+    if (b.kind != UDP_OP_CONV || b.ks != 1 || b.stride != 1 || b.wfmt != 1 || b.out_buf != UDP_BUF_OUTPUT || b.res_buf != UDP_BUF_NONE ||
+        b.n_up || b.relu || b.n_out2 || b.chain_cout || b.group || b.in_stuff2 || b.in_buf != a.out_buf || b.in_coff ||
+        (b.in_pitch && b.in_pitch != a.cout) || b.cin != a.cout || b.lane != a.lane)
+      continue;
+    // nobody else reads the intermediate map (any later mention of the buffer counts, whatever is written in between)
+    bool shared = false;
+    for (size_t k = i + 2; k < h->ops.size() && !shared; ++k) {
+      const udp_conv_op& o = h->ops[k];
+      shared = o.in_buf == a.out_buf || o.res_buf == a.out_buf || (o.chain_cout && o.chain_buf == a.out_buf);
+      for (int u = 0; u < o.n_up && u < 3; ++u) shared |= o.up_buf[u] == a.out_buf;
+      for (int u = 0; u < o.n_out2 && u < 2; ++u) shared |= o.add2_buf[u] == a.out_buf || o.out2_buf[u] == a.out_buf;
+    }
+    if (shared) continue;
+    Launch fused;
+    const int rc = describe_head_chain(L[i].p, L[i + 1].p, &fused);
+    if (rc == 1) continue;       // no instantiation for these widths
+    if (rc) return rc;
+    fused.pair = 1;
+    L[i] = fused;
+    ++i;
+  }
+  return UDP_OK;
+}
+
+// out_skip: ConvParams::out_skip of the ops that write UDP_BUF_OUTPUT (0: the plain [images | mirrored] layout at `out`).
+static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, int out_skip, char* ws, float* out,
                         std::vector<Launch>& ls) {
   const int B = n * (flip ? 2 : 1);
   const size_t es = esize(h->dtype);
@@ -437,6 +483,7 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
     p.res_coff = o.res_coff;
     p.in = is_stem ? reinterpret_cast<const void*>(in) : buf(o.in_buf);
     p.out_nchw_f32 = o.out_buf == UDP_BUF_OUTPUT;
+    p.out_skip = p.out_nchw_f32 ? out_skip : 0;     // (a writer without the field refuses a non-zero value: describe_conv)
     p.out = p.out_nchw_f32 ? reinterpret_cast<void*>(out) : o.out_buf == UDP_BUF_NONE ? nullptr : buf(o.out_buf);
     p.res = o.res_buf == UDP_BUF_NONE ? nullptr : buf(o.res_buf);
     p.nup = o.n_up;
@@ -514,10 +561,11 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, ch
     }
     if (rc) return rc;
   }
-  return UDP_OK;
+  return mark_head_chain(h, ls);
 }
 
-// Launch list: runs of groupable convs with the same group id become one conv_mfma_multi launch.
+// Launch list: runs of groupable convs with the same group id become one conv_mfma_multi launch; a chained head pair
+// (Launch::pair) is one node of two ops.
 struct Node {
   size_t first;
   int n;
@@ -527,16 +575,19 @@ static std::vector<Node> make_nodes(const udp_hrnet* h, const std::vector<Launch
   *grouped = false;
   for (size_t i = 0; i < L.size();) {
     int n = 1;
-    if (L[i].groupable && h->ops[i].group != 0)
+    if (L[i].pair) {
+      n = 2;                      // (both ops on one lane: no reason to give up the lanes, `grouped` stays)
+    } else if (L[i].groupable && h->ops[i].group != 0) {
       while (n < 4 && i + n < L.size() && L[i + n].groupable / 10 == L[i].groupable / 10 && h->ops[i + n].group == h->ops[i].group) ++n;
+      *grouped |= n > 1;
+    }
     nodes.push_back({i, n});
-    *grouped |= n > 1;
     i += n;
   }
   return nodes;
 }
 static int run_node(const std::vector<Launch>& L, const Node& nd, hipStream_t s) {
-  if (nd.n == 1) return run_launch(L[nd.first], s);
+  if (nd.n == 1 || L[nd.first].pair) return run_launch(L[nd.first], s);
   ConvMulti m;
   Launch ml;
   const int rc = describe_multi(&L[nd.first], nd.n, &m, &ml);
@@ -575,14 +626,18 @@ static int enqueue_all(udp_hrnet* h, const std::vector<Launch>& L, hipStream_t s
   for (size_t i = 0; i < h->ops.size(); ++i) {
     const udp_conv_op& o = h->ops[i];
     hipStream_t os = ls[o.lane];
+    const size_t last = i + (L[i].pair ? 1 : 0);      // a chained head pair: one launch for ops i and i + 1 (same lane)
     if (lanes)
-      for (int k = 0; k < o.n_wait; ++k)
-        if (h->ops[o.wait_op[k]].lane != o.lane) UDP_HIP_CHECK(hipStreamWaitEvent(os, h->op_done[o.wait_op[k]], 0));
+      for (size_t j = i; j <= last; ++j)
+        for (int k = 0; k < h->ops[j].n_wait; ++k)
+          if (h->ops[h->ops[j].wait_op[k]].lane != o.lane) UDP_HIP_CHECK(hipStreamWaitEvent(os, h->op_done[h->ops[j].wait_op[k]], 0));
     if (ev) UDP_HIP_CHECK(hipEventRecord(ev[2 * i], os));
     const int rc = run_launch(L[i], os);
     if (rc) return rc;
     if (ev) UDP_HIP_CHECK(hipEventRecord(ev[2 * i + 1], os));
-    if (lanes && h->op_signals[i]) UDP_HIP_CHECK(hipEventRecord(h->op_done[i], os));
+    for (size_t j = i; j <= last; ++j)
+      if (lanes && h->op_signals[j]) UDP_HIP_CHECK(hipEventRecord(h->op_done[j], os));
+    i = last;
   }
   if (lanes)
     for (int l = 1; l < h->n_lanes; ++l) {
@@ -611,13 +666,15 @@ static int build_graph(udp_hrnet* h, const std::vector<Launch>& L, hipGraph_t* g
       if (k) deps.push_back(node[k - 1]);
     } else {
       if (last_on_lane[o.lane] >= 0) deps.push_back(node[last_on_lane[o.lane]]);
-      for (int w = 0; w < o.n_wait; ++w) deps.push_back(node[node_of_op[o.wait_op[w]]]);
+      for (int j = 0; j < nodes[k].n; ++j)       // (n > 1 here: a chained head pair, whose second op may wait on the first)
+        for (int w = 0; w < h->ops[i + j].n_wait; ++w)
+          if ((size_t)h->ops[i + j].wait_op[w] < i) deps.push_back(node[node_of_op[h->ops[i + j].wait_op[w]]]);
     }
     ConvParams p = L[i].p;
     ConvMulti m;
     Launch ml = L[i];
     void* args[1] = {&p};
-    if (nodes[k].n > 1) {
+    if (nodes[k].n > 1 && !L[i].pair) {
       const int rc = describe_multi(&L[i], nodes[k].n, &m, &ml);
       if (rc) {
         (void)hipGraphDestroy(*graph);
@@ -666,7 +723,7 @@ extern "C" int udp_hrnet_profile(udp_hrnet* h, const float* in_nchw, int n, int 
   if (!ms_per_op) return fail(UDP_ERR_ARG, "udp_hrnet_profile: null pointer");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   std::vector<Launch> L;
-  rc = describe_all(h, in_nchw, n, flip_test ? 1 : 0, reinterpret_cast<char*>(workspace), heatmaps_nchw, L);
+  rc = describe_all(h, in_nchw, n, flip_test ? 1 : 0, 0, reinterpret_cast<char*>(workspace), heatmaps_nchw, L);
   if (rc) return rc;
   const size_t nops = h->ops.size();
   std::vector<hipEvent_t> ev(2 * nops, nullptr);
@@ -698,13 +755,13 @@ extern "C" int udp_hrnet_profile(udp_hrnet* h, const float* in_nchw, int n, int 
   return UDP_OK;
 }
 
-static int forward_one(udp_hrnet* h, const float* in_nchw, int n, int flip_test, void* workspace, float* heatmaps_nchw,
-                       int use_graph, hipStream_t s) {
+static int forward_one(udp_hrnet* h, const float* in_nchw, int n, int flip_test, int out_skip, void* workspace,
+                       float* heatmaps_nchw, int use_graph, hipStream_t s) {
   int rc;
   if (use_graph)
     for (size_t k = 0; k < h->graphs.size(); ++k) {
       const GraphEntry g = h->graphs[k];
-      if (g.n == n && g.flip == flip_test && g.in == in_nchw && g.ws == workspace && g.out == heatmaps_nchw) {
+      if (g.n == n && g.flip == flip_test && g.skip == out_skip && g.in == in_nchw && g.ws == workspace && g.out == heatmaps_nchw) {
         if (k + 1 != h->graphs.size()) {   // most recently used last
           h->graphs.erase(h->graphs.begin() + k);
           h->graphs.push_back(g);
@@ -714,13 +771,14 @@ static int forward_one(udp_hrnet* h, const float* in_nchw, int n, int flip_test,
       }
     }
   std::vector<Launch> L;
-  rc = describe_all(h, in_nchw, n, flip_test, reinterpret_cast<char*>(workspace), heatmaps_nchw, L);
+  rc = describe_all(h, in_nchw, n, flip_test, out_skip, reinterpret_cast<char*>(workspace), heatmaps_nchw, L);
   if (rc) return rc;
   if (!use_graph) return enqueue_all(h, L, s, nullptr, 1);
   // First call for this (shape, buffers): build the graph, then launch it.
   GraphEntry e;
   e.n = n;
   e.flip = flip_test;
+  e.skip = out_skip;
   e.in = in_nchw;
   e.ws = workspace;
   e.out = heatmaps_nchw;
@@ -745,7 +803,7 @@ extern "C" int udp_hrnet_forward(udp_hrnet* h, const float* in_nchw, int n, int 
   if (rc) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   flip_test = flip_test ? 1 : 0;
-  if (!use_graph || !split_ok(h, n)) return forward_one(h, in_nchw, n, flip_test, workspace, heatmaps_nchw, use_graph, s);
+  if (!use_graph || !split_ok(h, n)) return forward_one(h, in_nchw, n, flip_test, 0, workspace, heatmaps_nchw, use_graph, s);
   // ---- two sub-batch lanes
   if (!h->split_stream) {
     UDP_HIP_CHECK(hipStreamCreateWithFlags(&h->split_stream, hipStreamNonBlocking));
@@ -762,30 +820,50 @@ extern "C" int udp_hrnet_forward(udp_hrnet* h, const float* in_nchw, int n, int 
   const size_t img_in = (size_t)3 * h->in_h * h->in_w;
   const size_t img_out = out_bytes(h, 1) / sizeof(float);
   hipStream_t s2 = h->split_stream;
-  UDP_HIP_CHECK(hipEventRecord(h->split_fork, s));
-  UDP_HIP_CHECK(hipStreamWaitEvent(s2, h->split_fork, 0));
-  if (!flip_test) {
-    rc = forward_one(h, in_nchw, n0, 0, ws0, heatmaps_nchw, 1, s);
-    if (!rc) rc = forward_one(h, in_nchw + n0 * img_in, n1, 0, ws1, heatmaps_nchw + n0 * img_out, 1, s2);
+  // Between the fork and the join no HIP error returns: the first one is kept (with its message) and the join still
+  // runs, so that whatever was enqueued on the second stream is ordered before the caller's next work on `s`.
+  hipError_t he = hipSuccess;
+  const char* he_what = "";
+  auto hip_try = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && he == hipSuccess) {
+      he = e;
+      he_what = what;
+    }
+    return e == hipSuccess;
+  };
+  bool forked = hip_try(hipEventRecord(h->split_fork, s), "hipEventRecord(fork)");
+  forked = forked && hip_try(hipStreamWaitEvent(s2, h->split_fork, 0), "hipStreamWaitEvent(fork)");
+  if (!forked) {
+    // nothing runs on the second stream
+  } else if (!flip_test) {
+    rc = forward_one(h, in_nchw, n0, 0, 0, ws0, heatmaps_nchw, 1, s);
+    if (!rc) rc = forward_one(h, in_nchw + n0 * img_in, n1, 0, 0, ws1, heatmaps_nchw + n0 * img_out, 1, s2);
+  } else if (h->out_in_place && (size_t)2 * n * img_out * sizeof(float) < 0x7FFF0000u) {
+    // a lane's heat-maps are [its images | their mirrored copies]; the caller's layout is [all images | all mirrored]:
+    // the output writers put a lane's mirrored rows behind ALL the plain images themselves (ConvParams::out_skip), a
+    // writer that cannot makes the lane fail with UDP_ERR_UNSUPPORTED (describe_conv) and writes nothing
+    rc = forward_one(h, in_nchw, n0, 1, n - n0, ws0, heatmaps_nchw, 1, s);
+    if (!rc) rc = forward_one(h, in_nchw + n0 * img_in, n1, 1, n0, ws1, heatmaps_nchw + n0 * img_out, 1, s2);
   } else {
-    // a lane's heat-maps are [its images | their mirrored copies]; the caller's layout is [all images | all mirrored]
+    // staged: each lane writes [its images | mirrored] behind the workspaces, four copies put the halves into place
     float* t0 = reinterpret_cast<float*>(ws1 + ws_bytes_one(h, n1, 1));
     float* t1 = t0 + 2 * n0 * img_out;
-    rc = forward_one(h, in_nchw, n0, 1, ws0, t0, 1, s);
+    rc = forward_one(h, in_nchw, n0, 1, 0, ws0, t0, 1, s);
     if (!rc) {
-      UDP_HIP_CHECK(hipMemcpyAsync(heatmaps_nchw, t0, n0 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s));
-      UDP_HIP_CHECK(hipMemcpyAsync(heatmaps_nchw + n * img_out, t0 + n0 * img_out, n0 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s));
-      rc = forward_one(h, in_nchw + n0 * img_in, n1, 1, ws1, t1, 1, s2);
+      hip_try(hipMemcpyAsync(heatmaps_nchw, t0, n0 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(lane 0)");
+      hip_try(hipMemcpyAsync(heatmaps_nchw + n * img_out, t0 + n0 * img_out, n0 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(lane 0, mirrored)");
+      rc = forward_one(h, in_nchw + n0 * img_in, n1, 1, 0, ws1, t1, 1, s2);
     }
     if (!rc) {
-      UDP_HIP_CHECK(hipMemcpyAsync(heatmaps_nchw + n0 * img_out, t1, n1 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s2));
-      UDP_HIP_CHECK(hipMemcpyAsync(heatmaps_nchw + (n + n0) * img_out, t1 + n1 * img_out, n1 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s2));
+      hip_try(hipMemcpyAsync(heatmaps_nchw + n0 * img_out, t1, n1 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s2), "hipMemcpyAsync(lane 1)");
+      hip_try(hipMemcpyAsync(heatmaps_nchw + (n + n0) * img_out, t1 + n1 * img_out, n1 * img_out * sizeof(float), hipMemcpyDeviceToDevice, s2), "hipMemcpyAsync(lane 1, mirrored)");
     }
   }
-  // join (also after an error in a lane: whatever was enqueued on the second stream is ordered before the caller's next work)
-  UDP_HIP_CHECK(hipEventRecord(h->split_join, s2));
-  UDP_HIP_CHECK(hipStreamWaitEvent(s, h->split_join, 0));
-  return rc;
+  // join: always, also after an error in a lane or in a copy
+  if (forked && hip_try(hipEventRecord(h->split_join, s2), "hipEventRecord(join)")) hip_try(hipStreamWaitEvent(s, h->split_join, 0), "hipStreamWaitEvent(join)");
+  if (rc) return rc;
+  if (he != hipSuccess) return fail(UDP_ERR_HIP, "udp_hrnet_forward: %s failed: %s", he_what, hipGetErrorString(he));
+  return UDP_OK;
 }
 
 extern "C" int udp_hrnet_destroy(udp_hrnet* h) {
