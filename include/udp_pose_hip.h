@@ -245,7 +245,54 @@ enum udp_op_kind {
    * of 8); `out` MAY be `in` (same buffer, same view): every element is read and written by one thread.  No weights /
    * bias (may be NULL), addends, second outputs, chain, group, wfmt.  The arithmetic is that of the activation codes
    * below, fp32; act(0) = 0, so zero pad channels stay exact zeros.  Not counted in udp_hrnet_flops_per_image. */
-  UDP_OP_ACT = 19
+  UDP_OP_ACT = 19,
+  /* Kinds 20 - 22: the gates of RSN-18 "se + prm" (RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py).  All three:
+   * UDP_F32 and UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED); inputs decoded hi + lo * 2^-11, results split again on store
+   * with the udp_f16x2_overflow range guard; parameters fp32 in EVERY storage mode; per image, nothing atomic, every
+   * sum in an order that depends on the shape only: an image's result does not depend on the batch it arrives in, on
+   * the lane or on graph replay.  sigmoid(v) = 1 / (1 + expf(-v)) in fp32.  They add kinds and no field or symbol:
+   * UDP_POSE_ABI_VERSION stays as it is.
+   *
+   * Squeeze-and-excitation with the block's shortcut (SELayer, reduction 8, no biases, no BatchNorm: network.py:51-66;
+   * `out = se(out); out += x; relu`, :137-143) on an NHWC view of C stored channels; one launch, one workgroup per image:
+   *   mean[c] = (1 / HW) sum_p in[p][c]      h = relu(W1 mean)      m = sigmoid(W2 h)
+   *   out[p][c] = act(fmaf(in[p][c], m[c], res[p][c]))         (res_buf == UDP_BUF_NONE: in[p][c] * m[c])
+   * cin == cout == cout_pad = C, a multiple of 32 up to 512; hout == hin, wout == win (any size >= 1); chain_cout = the
+   * hidden width Ch (rows of W1), 1 <= Ch <= 256 -- a count, as for kind 14, no chained conv.  relu = UDP_ACT_NONE or
+   * UDP_ACT_RELU (codes 2 and 4: UDP_ERR_UNSUPPORTED).  in / out / res views are honoured (multiples of 8).  `out` MAY
+   * be `in` (same buffer, same view -- the rule of kind 14): the pool is complete before the first store and every
+   * element is read and written by one thread; any other overlap of the two, and `res` in the buffer of `in` or `out`,
+   * is refused.  No up-sampled addends, second outputs, group, wfmt.  Parameter block at w_off (udp_conv2d_fused:
+   * `weights`; `bias` may be NULL): W1 transposed [C][Ch], W2 transposed [Ch][C]; zero weights at pad channels give
+   * m = 0.5 there, and act(0 * 0.5 + 0) = 0 keeps them exact zeros.  Sums as kind 14: the pool by P pixel groups per
+   * channel added in group order, W1 mean by Q channel parts (fmaf from 0 in channel order) added in part order, W2 h by
+   * fmaf from 0 in the order j = 0 .. Ch-1; P, Q depend on (C, Ch) only.  udp_hrnet_flops_per_image counts 4 C Ch. */
+  UDP_OP_SE_RES = 20,
+  /* Channel gate of the Pose Refine Machine (PRM.forward, network.py:293-296): in = out_1 on an NHWC view of C stored
+   * channels; out = ONE fp32 row a[C] per image in a side buffer of C floats (counted in `dtype` elements, the way
+   * UDP_OP_PSA_MLP leaves its vector); one launch, one workgroup per image:
+   *   a = sigmoid(relu(W2 relu(W1 mean_p in + b1) + b2))
+   * -- the ReLU in front of the sigmoid is the reference's (conv_bn_relu(..., has_relu=True), :278-281).  The conv biases
+   * and BatchNorms of prm_2_1 / prm_2_2 are folded into W / b on the host (in fp64).  cin == cout == cout_pad = C, a
+   * multiple of 32 up to 256 (the hidden layer is C wide); hin x win = the map, hout == hin, wout == win; the input view
+   * is honoured, the output takes none; chain_cout 0, relu 0, no res / addends / second outputs / group / wfmt; `out`
+   * must not be `in`.  Parameter block at w_off (udp_conv2d_fused: `weights`; `bias` may be NULL): W1 transposed [C][C],
+   * b1 [C], W2 transposed [C][C], b2 [C].  Sums as kind 20, onto b1 / from b2.  Counts 4 C C in udp_hrnet_flops_per_image. */
+  UDP_OP_PRM_GATE = 21,
+  /* Spatial gate of the Pose Refine Machine and the combine (network.py:297-300): a depthwise Conv2d(C, C, 9, 1, 4,
+   * groups=C) with bias + folded BatchNorm + ReLU + sigmoid, then out_1 * (1 + channel gate * spatial gate):
+   *   in = t (the output of the 1x1 prm_3_1), res = out_1, n_up = 1 with up_buf[0] = the fp32 rows of kind 21 and
+   *   up_shift[0] = 0 (udp_conv2d_fused: `res`, `up0`)
+   *   out[p][c] = res[p][c] * fmaf(a[c], sigmoid(max(dw9(t)[p][c], 0)), 1)
+   * dw9 has the arithmetic contract of kind 12: acc = bias, then one fmaf per tap in the order ky = 0..8, kx = 0..8,
+   * a tap outside the image skipped (not read, not multiplied by zero) -- so the result does not depend on the tiling.
+   * Weights fp32 [81][C], tap-major (tap = 9 ky + kx), the BatchNorm scale folded in; bias fp32 [C] (conv bias and
+   * BatchNorm folded).  ks = 9, stride = 1 (anything else: UDP_ERR_ARG); cin == cout == cout_pad = C, a multiple of 32;
+   * hout == hin, wout == win, any size >= 1 (maps smaller than the window included).  in / out / res views are
+   * honoured (multiples of 8).  `out` must not be `in` or `res`.  relu 0; no second outputs, chain, group, wfmt.  An
+   * LDS-tiled VALU kernel (csrc/rsn_gate.hip): the 16 x 24 pixel input tile of an 8 x 16 output tile is staged once.
+   * udp_hrnet_flops_per_image counts the 81 MACs per output element. */
+  UDP_OP_PRM_DW9 = 22
 };
 
 /* udp_conv_op.relu is an activation code.  UDP_ACT_HSWISH: v * (clamp(v + 3, 0, 6) / 6) in fp32, applied where the
@@ -268,7 +315,7 @@ enum udp_op_kind {
 
 typedef struct udp_conv_op {
   int32_t kind;            /* enum udp_op_kind */
-  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7; pad = ks/2; UDP_OP_LINATTN / UDP_OP_MHATTN: 2 = the patch size), stride 1|2 */
+  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7, UDP_OP_PRM_DW9: 9; pad = ks/2; UDP_OP_LINATTN / UDP_OP_MHATTN: 2 = the patch size), stride 1|2 */
   int32_t relu;            /* activation of the epilogue: UDP_ACT_NONE / UDP_ACT_RELU / UDP_ACT_HSWISH / UDP_ACT_SILU (see there) */
   int32_t cin, cout;       /* real channel counts (cin multiple of 16 for UDP_OP_CONV) */
   int32_t cout_pad;        /* cout rounded up to a multiple of 32: rows of `weights`/`bias` */
@@ -361,10 +408,11 @@ double udp_hrnet_flops_per_image(const udp_hrnet* h);
 
 /* One fused conv launch on raw pointers (the operator the program above is made of; used by
  * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE,
- * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM, UDP_OP_LINATTN, UDP_OP_LNORM, UDP_OP_MHATTN or UDP_OP_ACT: NHWC in / out, weights as documented there, no res / up -- except the
+ * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM, UDP_OP_LINATTN, UDP_OP_LNORM, UDP_OP_MHATTN, UDP_OP_ACT, UDP_OP_SE_RES, UDP_OP_PRM_GATE or UDP_OP_PRM_DW9: NHWC in / out, weights as documented there, no res / up -- except the
  * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`; UDP_OP_SE / UDP_OP_GNORM: `weights` = the parameter block, chain_cout = hidden width / real channels;
  * UDP_OP_LNORM: `weights` = the parameter block, chain_cout = real channels; UDP_OP_MHATTN: no weights, chain_cout = real width, up_shift[0] = heads;
- * UDP_OP_LINATTN / UDP_OP_ACT: no weights), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
+ * UDP_OP_LINATTN / UDP_OP_ACT: no weights; UDP_OP_SE_RES: `weights` = the parameter block, chain_cout = hidden width, `res` = the shortcut or NULL;
+ * UDP_OP_PRM_GATE: `weights` = the parameter block, `out` = fp32 [n][C]; UDP_OP_PRM_DW9: `res` = out_1, `up0` = the fp32 rows of UDP_OP_PRM_GATE), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;
  * its buffer ids and blob offsets are ignored except out_buf == UDP_BUF_OUTPUT, which selects
  * the NCHW fp32 output form.  in/res/ups/out: NHWC `dtype`; weights [ks*ks][cout_pad][cin]
  * `dtype`; bias fp32 [cout_pad].  Replaces conv+BN(+add)(+ReLU), pose_hrnet.py:43-59.

@@ -17,6 +17,7 @@ UDP_OP_STEM, UDP_OP_CONV, UDP_OP_FUSE, UDP_OP_STEM7, UDP_OP_MAXPOOL, UDP_OP_BILI
 UDP_OP_PSA_POOL, UDP_OP_PSA_MLP, UDP_OP_PSA_SCALE, UDP_OP_PSA_SP, UDP_OP_BLOCK = 6, 7, 8, 9, 10
 UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM, UDP_OP_LINATTN = 11, 12, 13, 14, 15, 16
 UDP_OP_LNORM, UDP_OP_MHATTN, UDP_OP_ACT = 17, 18, 19
+UDP_OP_SE_RES, UDP_OP_PRM_GATE, UDP_OP_PRM_DW9 = 20, 21, 22       # the gates of RSN-18 "se + prm" (csrc/rsn_gate.hip)
 UDP_ACT_NONE, UDP_ACT_RELU, UDP_ACT_HSWISH, UDP_ACT_SILU = 0, 1, 2, 4      # udp_conv_op.relu is an activation code (3: not assigned)
 UDP_BUF_NONE, UDP_BUF_OUTPUT = -1, -2
 ABI_VERSION = 19

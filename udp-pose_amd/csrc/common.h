@@ -175,6 +175,14 @@ int describe_lnorm(ConvParams p, int dtype, Launch* out);
 int describe_mhattn(ConvParams p, int dtype, Launch* out);
 int describe_act(ConvParams p, int dtype, Launch* out);
 int attn_h2_overflow(hipStream_t s, int reset, int* flag);
+// rsn_gate.hip: the SE layer with residual (UDP_OP_SE_RES), the channel gate (UDP_OP_PRM_GATE) and the depthwise 9x9
+// spatial gate + combine (UDP_OP_PRM_DW9) of RSN-18 "se + prm"
+int se_res_validate(const udp_conv_op& o, int dtype);
+int prm_gate_validate(const udp_conv_op& o, int dtype);
+int prm_dw9_validate(const udp_conv_op& o, int dtype);
+int describe_gate(ConvParams p, int dtype, bool prm, Launch* out);
+int describe_prm_dw9(ConvParams p, int dtype, Launch* out);
+int rsn_gate_h2_overflow(hipStream_t s, int reset, int* flag);
 int conv_h2_overflow(hipStream_t s, int reset, int* flag);       // conv.hip / conv_ws.hip / psa.hip: their g_h2_overflow
 int conv_ws_h2_overflow(hipStream_t s, int reset, int* flag);
 int psa_h2_overflow(hipStream_t s, int reset, int* flag);

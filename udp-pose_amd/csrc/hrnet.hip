@@ -80,7 +80,7 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
   const int nb = (int)h->buf_elems.size();
   auto buf_ok = [&](int b, int64_t need) { return b >= 0 && b < nb && h->buf_elems[b] >= need; };
   const int64_t out_need = (int64_t)o.hout * o.wout * (o.out_pitch ? o.out_pitch : o.cout);
-  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_ACT) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_PRM_DW9) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
   if (const int rc = act_validate(o, h->dtype, o.res_buf != UDP_BUF_NONE)) return rc;
   if (o.lane < 0 || o.lane >= UDP_MAX_LANES || o.n_wait < 0 || o.n_wait > UDP_MAX_WAIT) return fail(UDP_ERR_ARG, "op %d: lane/n_wait", idx);
   for (int k = 0; k < o.n_wait; ++k)
@@ -131,6 +131,34 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
     const size_t wbytes = ((size_t)2 * o.cin * o.chain_cout + o.chain_cout) * 4;
     if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15))
       return fail(UDP_ERR_ARG, "op %d: squeeze-excitation parameter block outside the blob or misaligned", idx);
+    return UDP_OK;
+  }
+  if (o.kind == UDP_OP_SE_RES || o.kind == UDP_OP_PRM_GATE || o.kind == UDP_OP_PRM_DW9) {
+    // the gates of RSN-18 "se + prm" (rsn_gate.hip); the SE layer's `out` may be the very view `in` is
+    const char* what = o.kind == UDP_OP_SE_RES ? "se + residual" : o.kind == UDP_OP_PRM_GATE ? "prm channel gate" : "prm spatial gate";
+    const int rc = o.kind == UDP_OP_SE_RES ? se_res_validate(o, h->dtype) : o.kind == UDP_OP_PRM_GATE ? prm_gate_validate(o, h->dtype) : prm_dw9_validate(o, h->dtype);
+    if (rc) return rc;
+    const int64_t hw = (int64_t)o.hin * o.win;
+    const int ipitch = o.in_pitch ? o.in_pitch : o.cin, rpitch = o.res_pitch ? o.res_pitch : o.cout;
+    const int64_t rows = (int64_t)o.cin * (4 / (int64_t)esize(h->dtype));        // an fp32 row a[C], counted in `dtype` elements
+    if (!buf_ok(o.in_buf, hw * ipitch) || !buf_ok(o.out_buf, o.kind == UDP_OP_PRM_GATE ? rows : out_need))
+      return fail(UDP_ERR_ARG, "op %d: %s buffers missing or too small", idx, what);
+    if (o.kind == UDP_OP_PRM_GATE ? o.res_buf != UDP_BUF_NONE : (o.res_buf != UDP_BUF_NONE || o.kind == UDP_OP_PRM_DW9) && !buf_ok(o.res_buf, hw * rpitch))
+      return fail(UDP_ERR_ARG, "op %d: %s: res_buf", idx, what);
+    if (o.kind == UDP_OP_SE_RES) {
+      if (o.in_buf == o.out_buf && (o.in_coff != o.out_coff || ipitch != (o.out_pitch ? o.out_pitch : o.cout)))
+        return fail(UDP_ERR_ARG, "op %d: se + residual in place needs the same view for in and out", idx);
+      if (o.res_buf == o.out_buf || o.res_buf == o.in_buf) return fail(UDP_ERR_ARG, "op %d: se + residual: res must not be in or out", idx);
+    } else if (o.in_buf == o.out_buf || o.res_buf == o.out_buf) {
+      return fail(UDP_ERR_ARG, "op %d: %s: out must not be in or res", idx, what);
+    }
+    if (o.kind == UDP_OP_PRM_DW9 && (!buf_ok(o.up_buf[0], rows) || o.up_buf[0] == o.out_buf))
+      return fail(UDP_ERR_ARG, "op %d: prm spatial gate: up_buf[0] (the channel gate's rows) missing, too small or the output", idx);
+    const size_t C = (size_t)o.cin;
+    const size_t wbytes = (o.kind == UDP_OP_SE_RES ? 2 * C * o.chain_cout : o.kind == UDP_OP_PRM_GATE ? 2 * C * C + 2 * C : 81 * C) * 4;
+    if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15) ||
+        (o.kind == UDP_OP_PRM_DW9 && (o.b_off < 0 || (size_t)o.b_off + C * 4 > h->weights_bytes || (o.b_off & 15))))
+      return fail(UDP_ERR_ARG, "op %d: %s parameter block outside the blob or misaligned", idx, what);
     return UDP_OK;
   }
   if (o.kind == UDP_OP_GNORM || o.kind == UDP_OP_LINATTN) {
@@ -299,6 +327,7 @@ extern "C" int udp_f16x2_overflow(void* stream, int reset) {
   if (!rc) rc = deconv_h2_overflow(s, reset, &flag);
   if (!rc) rc = dwconv_h2_overflow(s, reset, &flag);
   if (!rc) rc = attn_h2_overflow(s, reset, &flag);
+  if (!rc) rc = rsn_gate_h2_overflow(s, reset, &flag);
   return rc ? rc : flag;
 }
 
@@ -343,6 +372,9 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
     if (ops[i].kind == UDP_OP_DECONV) h->flops += 2.0 * 4 * ops[i].cin * ops[i].cout * ops[i].hout * ops[i].wout;   // 2x2 taps per output pixel
     if (ops[i].kind == UDP_OP_DWCONV) h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cout * ops[i].hout * ops[i].wout;   // ks * ks MACs per output element
     if (ops[i].kind == UDP_OP_SE) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // the two small products (pool and scale are not counted)
+    if (ops[i].kind == UDP_OP_SE_RES) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // as UDP_OP_SE
+    if (ops[i].kind == UDP_OP_PRM_GATE) h->flops += 2.0 * 2 * ops[i].cin * ops[i].cin;
+    if (ops[i].kind == UDP_OP_PRM_DW9) h->flops += 2.0 * 81 * ops[i].cout * ops[i].hout * ops[i].wout;   // the taps (the gate's epilogue is not counted)
     if (ops[i].kind == UDP_OP_LINATTN) h->flops += 2.0 * ops[i].cout * ops[i].hout * ops[i].wout;   // the weighted sum of the keys (soft-max and gate are not counted)
     if (ops[i].kind == UDP_OP_MHATTN)      // q k^T and the weighted sum of the values: 2 d N MACs per pixel, N = HW / 4 keys
       h->flops += 2.0 * 2 * ops[i].chain_cout * (ops[i].hout * ops[i].wout / 4) * ops[i].hout * ops[i].wout;
@@ -500,7 +532,7 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, in
       p.add2_coff[k] = o.add2_coff[k];
       p.add2_pitch[k] = o.add2_pitch[k] ? o.add2_pitch[k] : o.cout;
     }
-    if (is_stem || o.kind == UDP_OP_CONV || o.kind == UDP_OP_DECONV || o.kind == UDP_OP_DWCONV) {
+    if (is_stem || o.kind == UDP_OP_CONV || o.kind == UDP_OP_DECONV || o.kind == UDP_OP_DWCONV || o.kind == UDP_OP_PRM_DW9) {
       p.wgt = h->weights + o.w_off;
       p.bias = reinterpret_cast<const float*>(h->weights + o.b_off);
     }
@@ -520,6 +552,10 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, in
     if (o.kind == UDP_OP_MHATTN) {
       p.up_shift[0] = o.chain_cout;                              // real width d
       p.up_shift[1] = o.up_shift[0];                             // heads (mhattn_validate: n_up == 0)
+    }
+    if (o.kind == UDP_OP_SE_RES || o.kind == UDP_OP_PRM_GATE) {
+      p.wgt = h->weights + o.w_off;
+      p.up_shift[0] = o.kind == UDP_OP_SE_RES ? o.chain_cout : o.cin;      // hidden width (n_up == 0)
     }
     if (o.kind == UDP_OP_BLOCK) {
       p.wgt = h->weights + o.w_off;
@@ -550,6 +586,9 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, in
       case UDP_OP_LNORM: rc = describe_lnorm(p, h->dtype, &ls[i]); break;
       case UDP_OP_MHATTN: rc = describe_mhattn(p, h->dtype, &ls[i]); break;
       case UDP_OP_ACT: rc = describe_act(p, h->dtype, &ls[i]); break;
+      case UDP_OP_SE_RES: rc = describe_gate(p, h->dtype, false, &ls[i]); break;
+      case UDP_OP_PRM_GATE: rc = describe_gate(p, h->dtype, true, &ls[i]); break;
+      case UDP_OP_PRM_DW9: rc = describe_prm_dw9(p, h->dtype, &ls[i]); break;
       case UDP_OP_PIXSHUF: rc = describe_pixshuf(p, h->dtype, &ls[i]); break;
       default:
         if (o.chain_cout) {
@@ -918,16 +957,29 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (n <= 0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: n=%d", n);
   if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV && o->kind != UDP_OP_DWCONV && o->kind != UDP_OP_PIXSHUF &&
       o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_LNORM && o->kind != UDP_OP_MHATTN &&
-      o->kind != UDP_OP_ACT)
+      o->kind != UDP_OP_ACT && o->kind != UDP_OP_SE_RES && o->kind != UDP_OP_PRM_GATE && o->kind != UDP_OP_PRM_DW9)
     return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
   if (const int rc = act_validate(*o, dtype, res != nullptr)) return rc;
-  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_MHATTN && o->kind != UDP_OP_ACT && (!weights || (!bias && o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LNORM))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_MHATTN && o->kind != UDP_OP_ACT && (!weights || (!bias && o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LNORM && o->kind != UDP_OP_SE_RES && o->kind != UDP_OP_PRM_GATE))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
   if (o->kind == UDP_OP_SE) {
     const int rc = se_validate(*o, dtype);
     if (rc) return rc;
     if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation takes no residual");
     if (in == out && (o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
       return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation in place needs the same view for in and out");
+  }
+  if (o->kind == UDP_OP_SE_RES || o->kind == UDP_OP_PRM_GATE || o->kind == UDP_OP_PRM_DW9) {
+    // the gates of RSN-18 "se + prm": `res` = the shortcut (optional) / -- / out_1; UDP_OP_PRM_DW9: `up0` = the channel gate's fp32 rows
+    const int rc = o->kind == UDP_OP_SE_RES ? se_res_validate(*o, dtype) : o->kind == UDP_OP_PRM_GATE ? prm_gate_validate(*o, dtype) : prm_dw9_validate(*o, dtype);
+    if (rc) return rc;
+    if (o->kind == UDP_OP_SE_RES) {
+      if (in == out && (o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
+        return fail(UDP_ERR_ARG, "udp_conv2d_fused: se + residual in place needs the same view for in and out");
+      if (res && (res == in || res == out)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: se + residual: res must not be in or out");
+    } else {
+      if (o->kind == UDP_OP_PRM_GATE ? res != nullptr : !res || !up0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: prm gates: res / up0 (out_1 / the channel gate's rows) belong to the spatial gate alone");
+      if (in == out || res == out) return fail(UDP_ERR_ARG, "udp_conv2d_fused: prm gates: out must not be in or res");
+    }
   }
   if (o->kind == UDP_OP_GNORM || o->kind == UDP_OP_LINATTN) {
     const bool gn = o->kind == UDP_OP_GNORM;
@@ -979,6 +1031,8 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   p.relu = o->relu;
   if (o->kind == UDP_OP_SE || o->kind == UDP_OP_GNORM || o->kind == UDP_OP_LNORM) {
     p.up_shift[0] = o->chain_cout;      // hidden width / real channels (se_validate, gnorm_validate, lnorm_validate: n_up == 0, n_out2 == 0)
+  } else if (o->kind == UDP_OP_SE_RES || o->kind == UDP_OP_PRM_GATE) {
+    p.up_shift[0] = o->kind == UDP_OP_SE_RES ? o->chain_cout : o->cin;      // hidden width (n_up == 0, n_out2 == 0)
   } else if (o->kind == UDP_OP_MHATTN) {
     p.up_shift[0] = o->chain_cout;      // real width d
     p.up_shift[1] = o->up_shift[0];     // heads (mhattn_validate: n_up == 0, n_out2 == 0)
@@ -1011,6 +1065,10 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   p.wgt = weights;
   p.bias = bias;
   p.nup = o->n_up;
+  if (o->kind == UDP_OP_PRM_DW9) {      // n_up == 1: not an addend but the channel gate's fp32 rows (prm_dw9_validate)
+    p.up[0] = up0;
+    return UDP_OK;
+  }
   for (int u = 0; u < o->n_up; ++u) {
     const int s = o->up_shift[u];
     // (UDP_OP_FUSE also takes same-resolution addends, shift 0: the training step's exchange-unit sums have up to four terms)
@@ -1040,6 +1098,9 @@ static int conv2d_fused_impl(const udp_conv_op* o, int dtype, int n, const void*
                  : o->kind == UDP_OP_LNORM  ? describe_lnorm(p, dtype, &l)
                  : o->kind == UDP_OP_MHATTN ? describe_mhattn(p, dtype, &l)
                  : o->kind == UDP_OP_ACT    ? describe_act(p, dtype, &l)
+                 : o->kind == UDP_OP_SE_RES ? describe_gate(p, dtype, false, &l)
+                 : o->kind == UDP_OP_PRM_GATE ? describe_gate(p, dtype, true, &l)
+                 : o->kind == UDP_OP_PRM_DW9 ? describe_prm_dw9(p, dtype, &l)
                  : o->kind == UDP_OP_PIXSHUF ? describe_pixshuf(p, dtype, &l)
                                             : describe_conv(p, dtype, o->ks, o->stride, &l);
   if (rc) return rc;

@@ -309,22 +309,30 @@ class PoseHighResolutionNetHip(PoseNetHip):
 
 class RSN18Hip(PoseNetHip):
     """RSN-18 (RSN/exps/RSN18.coco/network.py, STAGE_NUM = 1) inference through the same C ABI;
-    ``state_dict`` in the reference module's key format; returns ``outputs[-1][-1]`` ([N,C,H/4,W/4])."""
+    ``state_dict`` in the reference module's key format; returns ``outputs[-1][-1]`` ([N,C,H/4,W/4]).
+    ``se`` / ``prm``: the SELayer in every Bottleneck and the Pose Refine Machine on the finest level, as in
+    RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py, on this net's stem (rsn_plan.py says why that experiment's own
+    checkpoints do not load); storage modes f32 and f16x2."""
 
     NAME = "RSN-18"
 
-    def __init__(self, out_channels=17, dtype="f32", chl_num=256):
+    def __init__(self, out_channels=17, dtype="f32", chl_num=256, se=False, prm=False):
+        if (se or prm) and dtype not in ("f32", "f16x2"):
+            raise ValueError("RSN-18 with se / prm: storage modes 'f32' and 'f16x2' only (got %r)" % (dtype,))
         super().__init__(None, dtype)
         self.out_channels = int(out_channels)
         self.chl_num = chl_num
+        self.se, self.prm = bool(se), bool(prm)
 
     def param_shapes(self):
-        from .synth import rsn18_param_shapes
+        from .synth import rsn18_param_shapes, rsn18_se_prm_param_shapes
+        if self.se or self.prm:
+            return rsn18_se_prm_param_shapes(self.out_channels, self.chl_num, self.se, self.prm)
         return rsn18_param_shapes(self.out_channels, self.chl_num)
 
     def _make_program(self, h, w):
         from .rsn_plan import RSNProgram
-        return RSNProgram(self._sd, h, w, self.dtype, self.chl_num)
+        return RSNProgram(self._sd, h, w, self.dtype, self.chl_num, self.se, self.prm)
 
 
 def get_pose_net(cfg, is_train, **kwargs):

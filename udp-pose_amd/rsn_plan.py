@@ -11,16 +11,28 @@ multiple of 16 channels (26 -> 32, 52 -> 64, 104 -> 112, 208), the 1x1 conv's we
 closing 1x1 conv's weight columns are scattered to the padded positions with zeros in between, the
 3x3 convs read / write channel slices in place, and the pad channels stay exactly 0 (zero weights,
 zero bias, ReLU).  The ``a + b`` that precedes most 3x3 convs is one element-wise launch.
+
+``se`` / ``prm``: the two additions of RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py, on THIS stem (that
+experiment's own ResNet_top, :188-203, holds a 7x7 stride-1 64 -> 64 conv that no kernel here covers: its checkpoints
+do not load).  ``se``: conv_bn_relu3 runs without residual and ReLU, and one UDP_OP_SE_RES launch follows in place with
+the shortcut as ``res`` and the ReLU on (:51-66, :135-143) -- 16 launches.  ``prm``: behind up4's ReLU the Pose Refine
+Machine (:267-301, :357-358) as 3x3 conv, UDP_OP_PRM_GATE, 1x1 conv, UDP_OP_PRM_DW9 -- 4 launches; res_conv1 reads the
+result.  Both need f32 / f16x2 storage.
 """
 import os
 
+import torch
+
 from . import _lib
-from .program import Program, _round_up
+from .program import Program, _round_up, storage_bytes
 
 
 class RSNProgram(Program):
-    def __init__(self, state_dict, in_h, in_w, dtype="f32", chl_num=256):
+    def __init__(self, state_dict, in_h, in_w, dtype="f32", chl_num=256, se=False, prm=False):
         self.chl_num = chl_num
+        self.se, self.prm = bool(se), bool(prm)
+        if (self.se or self.prm) and dtype not in ("f32", "f16x2"):
+            raise ValueError("RSN-18 with se / prm: storage modes 'f32' and 'f16x2' only (got %r)" % (dtype,))
         super().__init__(state_dict, in_h, in_w, dtype)
 
     def _fold_cbr(self, name):
@@ -109,7 +121,48 @@ class RSNProgram(Program):
         r = x
         if (p + ".downsample.conv.weight") in sd:
             r = self._conv_v(x, p + ".downsample", stride=stride, relu=False)
-        return self._conv_v(cat, p + ".conv_bn_relu3", res=r, in_map=scatter, cin_t=4 * bp)
+        if not self.se:
+            return self._conv_v(cat, p + ".conv_bn_relu3", res=r, in_map=scatter, cin_t=4 * bp)
+        out = self._conv_v(cat, p + ".conv_bn_relu3", relu=False, in_map=scatter, cin_t=4 * bp)
+        return self._se_res(out, p + ".se", r)
+
+    def _f32(self, key, shape):
+        if key not in self.sd:
+            raise ValueError("state_dict has no %s" % key)
+        t = self.sd[key].detach().to(torch.float32).cpu()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must be %s, got %s" % (key, list(shape), list(t.shape)))
+        return t
+
+    def _se_res(self, x, p, res):
+        """SELayer ``p`` (reduction 8, no biases) on ``x`` in place, then + ``res`` and ReLU: one UDP_OP_SE_RES launch."""
+        c, ch = x.c, x.c // 8
+        w1, w2 = self._f32(p + ".fc.0.weight", (ch, c)), self._f32(p + ".fc.2.weight", (c, ch))
+        w_off = self._put(torch.cat([w1.t().reshape(-1), w2.t().reshape(-1)]).contiguous().numpy().tobytes())
+        self._op(_lib.UDP_OP_SE_RES, x, x, p, res=res, relu=1, cin=c, cout=c, cout_pad=c, chain_cout=ch, w_off=w_off)
+        return x
+
+    def _prm(self, x, p):
+        """PRM.forward (network.py:290-301) on ``x`` -> a new tensor."""
+        c = x.c
+        out1 = self._conv_v(x, p + ".conv_bn_relu_prm_1")
+        blk = []
+        for nm in ("2_1", "2_2"):
+            w, b = self._fold_cbr(p + ".conv_bn_relu_prm_" + nm)
+            if tuple(w.shape) != (c, c, 1, 1):
+                raise ValueError("%s.conv_bn_relu_prm_%s.conv.weight must be [%d, %d, 1, 1]" % (p, nm, c, c))
+            blk += [w.reshape(c, c).t().reshape(-1), b]
+        rows = self._new(c * (4 // storage_bytes(self.dtype)), 1, 1)          # an fp32 row a[C] per image
+        self._emit(_lib.UDP_OP_PRM_GATE, p + ".gate", out1, rows, cin=c, cout=c, cout_pad=c, hout=out1.h, wout=out1.w,
+                   w_off=self._put(torch.cat(blk).contiguous().numpy().tobytes()))
+        t = self._conv_v(out1, p + ".conv_bn_relu_prm_3_1")
+        w, b = self._fold_cbr(p + ".conv_bn_relu_prm_3_2")
+        if tuple(w.shape) != (c, 1, 9, 9):
+            raise ValueError("%s.conv_bn_relu_prm_3_2.conv.weight must be [%d, 1, 9, 9]" % (p, c))
+        out = self._new(c, x.h, x.w)
+        self._op(_lib.UDP_OP_PRM_DW9, t, out, p + ".conv_bn_relu_prm_3_2", res=out1, ks=9, cin=c, cout=c, cout_pad=c, ups=[(rows, 0)],
+                 w_off=self._put(w.reshape(c, 81).t().contiguous().numpy().tobytes()), b_off=self._put(b.numpy().tobytes()))
+        return out
 
     def _build(self):
         H, W = self.in_h, self.in_w
@@ -135,6 +188,8 @@ class RSNProgram(Program):
                 t = self._conv_v(big, p + ".up_conv", relu=False)
                 out = self._conv_v(xin, p + ".u_skip", relu=True, res=t)     # relu(u_skip(x) + up_conv(up))
             up = out
+        if self.prm:
+            out = self._prm(out, "stage0.upsample.up4.prm")
         r1 = self._conv_v(out, "stage0.upsample.up4.res_conv1", relu=True)
         # the closing bilinear resize to OUTPUT_SHAPE (:255) is the identity at the finest level
         if (out.h, out.w) != (H // 4, W // 4):

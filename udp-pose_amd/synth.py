@@ -348,6 +348,82 @@ def synth_rsn18_state_dict(out_channels=17, seed=0, bn_calib=None):
     return sd
 
 
+def rsn18_se_prm_param_shapes(out_channels=17, chl_num=256, se=True, prm=True):
+    """Ordered {key: shape} of the RSN-18 above with the Bottleneck of
+    RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py (``se``) and the Pose Refine Machine of its up4 (``prm``), in the
+    module's registration order.  That Bottleneck (:68-117) closes with ``se.fc.{0,2}`` (registered behind conv_bn_relu3,
+    before downsample) and takes its branch width from ``planes`` (planes * 26 // 64, :74), not from ``in_planes`` as
+    RSN18.coco's does: the first block of layers 2 - 4 is twice as wide inside.  ``prm`` is registered last in up4
+    (:337-345)."""
+    s = OrderedDict()
+    _cbr(s, "top.conv", 3, 64, 7)
+    in_planes = 64
+    for layer, planes in zip(range(1, 5), (64, 128, 256, 512)):
+        for b in range(2):
+            p = "stage0.downsample.layer%d.%d" % (layer, b)
+            bch = (planes if se else in_planes) * 26 // 64
+            _cbr(s, p + ".conv_bn_relu1", in_planes, 4 * bch, 1)
+            for nm in ("2_1_1", "2_2_1", "2_2_2", "2_3_1", "2_3_2", "2_3_3", "2_4_1", "2_4_2", "2_4_3", "2_4_4"):
+                _cbr(s, p + ".conv_bn_relu" + nm, bch, bch, 3)
+            _cbr(s, p + ".conv_bn_relu3", 4 * bch, planes, 1)
+            if se:
+                s[p + ".se.fc.0.weight"] = (planes // 8, planes)
+                s[p + ".se.fc.2.weight"] = (planes, planes // 8)
+            if b == 0 and (layer > 1 or in_planes != planes):
+                _cbr(s, p + ".downsample", in_planes, planes, 1)
+            in_planes = planes
+    for ind, cin in enumerate((512, 256, 128, 64)):
+        p = "stage0.upsample.up%d" % (ind + 1)
+        _cbr(s, p + ".u_skip", cin, chl_num, 1)
+        if ind > 0:
+            _cbr(s, p + ".up_conv", chl_num, chl_num, 1)
+        _cbr(s, p + ".res_conv1", chl_num, chl_num, 1)
+        _cbr(s, p + ".res_conv2", chl_num, out_channels, 3)
+    if prm:
+        p = "stage0.upsample.up4.prm.conv_bn_relu_prm_"
+        for nm, k in (("1", 3), ("2_1", 1), ("2_2", 1), ("3_1", 1)):
+            _cbr(s, p + nm, chl_num, chl_num, k)
+        _cbr(s, p + "3_2", 1, chl_num, 9)
+    return s
+
+
+def synth_rsn18_se_prm_state_dict(out_channels=17, seed=0, bn_calib=None, se=True, prm=True):
+    """The rules of synth_rsn18_state_dict on the keys above, plus: fc.0 weights N(0, 400 / fan_in) -- the pooled vector it sees is the closing
+    BatchNorm's bias, of order 0.05 -- and fc.2 weights N(0, 4 / fan_in), so that the SE gates spread over (0, 1); PRM BatchNorm weights in [0.8, 1.6] (the two gates see pre-activations of order 1)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sd = OrderedDict()
+    for name, shape in rsn18_se_prm_param_shapes(out_channels, 256, se, prm).items():
+        if name.endswith("num_batches_tracked"):
+            sd[name] = torch.tensor(0, dtype=torch.long)
+            continue
+        if name.endswith("running_mean"):
+            a = np.zeros(shape, np.float32)
+        elif name.endswith("running_var"):
+            a = np.ones(shape, np.float32)
+        elif ".se.fc." in name:
+            a = (rng.standard_normal(shape) * (20.0 if ".fc.0." in name else 2.0) / np.sqrt(shape[1])).astype(np.float32)
+        elif len(shape) == 4:
+            a = rng.standard_normal(shape).astype(np.float32) * np.float32(np.sqrt(2.0 / (shape[1] * shape[2] * shape[3])))
+        elif name.endswith("conv.bias"):
+            a = (rng.standard_normal(shape) * 0.02).astype(np.float32)
+        elif name.endswith("bn.weight"):
+            closing = "conv_bn_relu3" in name or "downsample" in name or "up_conv" in name or "u_skip" in name
+            a = rng.uniform(0.8, 1.6, shape) if ".prm." in name else rng.uniform(0.2, 0.4, shape) if closing else rng.uniform(0.4, 0.8, shape)
+            a = a.astype(np.float32)
+        else:
+            a = (rng.standard_normal(shape) * 0.05).astype(np.float32)
+        sd[name] = torch.from_numpy(a)
+    if bn_calib is not None:
+        for k, v in bn_calib.items():
+            if k in sd:
+                sd[k] = torch.from_numpy(np.asarray(v, dtype=np.float32).copy())
+        if "final.scale" in bn_calib:
+            f = float(np.asarray(bn_calib["final.scale"]))
+            for k in ("stage0.upsample.up4.res_conv2.bn.weight", "stage0.upsample.up4.res_conv2.bn.bias"):
+                sd[k] = sd[k] * f
+    return sd
+
+
 COCO_FLIP_PAIRS = [[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]]     # lib/dataset/coco.py:91-92
 COCO_UPPER_BODY = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10)                                              # coco.py:94
 
