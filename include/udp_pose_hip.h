@@ -591,6 +591,13 @@ int udp_debug_multi_order(const unsigned* tiles, const unsigned* ncby, const int
  * UDP_POSE_ABI_VERSION stays as it is. */
 int udp_debug_conv_tile(int dtype, int wfmt, int ks, int stride, int n, int hout, int wout, int cin, int cout,
                         int nchw_out, int grouped, int* out);
+/* Diagnostic, host only (no GPU, no HIP call): the shared-input sets the executor forms over an op list in UDP_F16X2
+ * (csrc/hrnet.hip, find_share_sets): the 3x3 stride-2 convs with 32 input channels and the 32-channel UDP_OP_FUSE that
+ * read one input view run as ONE launch at the position of the earliest of them, where the buffer ids allow it.
+ * carrier[i] = the op whose launch does op i's work (i itself for the carrying op), -1 for an op outside every set.
+ * The ops are not validated and UDP_POSE_NO_X0_SHARE is not read.  Returns the number of sets, -1 on a null argument.
+ * Adds a symbol only: UDP_POSE_ABI_VERSION stays as it is. */
+int udp_debug_x0_share(const udp_conv_op* ops, int n_ops, int* carrier);
 int udp_conv2d_wgrad_group(const udp_wgrad_item* items, int n_items, int dtype, void* stream);
 /* Up to 4 independent plain convs (same dtype and batch n) in as few launches as possible -- the same-depth convs
  * of the HRNet branches in the training step (pose_hrnet.py:253-256): members whose tile fits the merged kernel run

@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 
 #include "../../include/udp_pose_hip.h"
 
@@ -123,6 +124,16 @@ struct ConvMulti {
   unsigned tab[kMultiTab];
 };
 
+// Kernel argument of conv_ws_s2x_kernel: 1..3 stride-2 3x3 convs over the SAME 32-channel input view ("routes", one
+// tile geometry, at most 4 cout pairs in all) and, optionally, the element-wise sum that reads that view too.
+constexpr int kShareRoutes = 3;
+struct ConvShare {
+  ConvParams p[kShareRoutes];   // the routes; their tile fields are equal
+  ConvParams side;              // the UDP_OP_FUSE member (side.out == null: none); mRT / mTW: magic numbers of its patch
+  unsigned route;               // byte s: route of the workgroup's cout-pair slot s (wave s % CP)
+  unsigned lpair;               // byte s: that slot's pair inside its route (a slot without a route: 255)
+};
+
 }  // namespace udp
 
 namespace udp {
@@ -134,8 +145,16 @@ struct Launch {
   int groupable = 0;   // conv described by describe_conv_grouped: may be merged with its group siblings
   int ws_cp = 0;       // weight-stationary member: its cout pairs per workgroup
   int pair = 0;        // this launch also does the NEXT op's work (describe_head_chain): the executor skips that op's own launch
+  int carried = 0;     // this op's work is done by an EARLIER launch (mark_x0_share): it has no launch of its own
+  int n_carry = 0;     // ops this launch carries (later in the program, not adjacent) ...
+  int carry[kShareRoutes] = {0, 0, 0};
+  int cross_lane = 0;  // ... some of them from another lane than this op's: the program runs as one chain
+  std::shared_ptr<ConvShare> share;   // ... and then its kernel argument (instead of `p`)
   ConvParams p;
 };
+// conv_ws.hip: one launch for convs[0..n) (3x3 stride 2 over one 32-channel view) and `fuse` (may be null); 1: no kernel
+// (`tag`: the members, for the UDP_POSE_DEBUG_TILES line)
+int describe_x0_share(const ConvParams* convs, int n, const ConvParams* fuse, const char* tag, Launch* out);
 // conv_ws.hip: the weight-stationary split-fp16 convs (tile choice + kernel of one conv; merged launch of 2..4)
 int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped = false);
 struct WsTile {

@@ -2012,7 +2012,7 @@ int describe_stem7(const ConvParams& p, int dtype, Launch* out) {
 }
 
 int run_launch(const Launch& l, hipStream_t s) {
-  void* args[] = {const_cast<ConvParams*>(&l.p)};
+  void* args[] = {l.share ? static_cast<void*>(l.share.get()) : const_cast<ConvParams*>(&l.p)};
   UDP_HIP_CHECK(hipLaunchKernel(l.fn, l.grid, l.block, args, l.lds, s));
   return UDP_OK;
 }

@@ -44,8 +44,9 @@ __device__ __forceinline__ void add_res_h2(f32x4 (&v)[NB], const ResH2<NB>& o) {
 
 // HS: the hard-swish / SiLU instantiations (HS = udp_conv_op.relu = UDP_ACT_HSWISH | UDP_ACT_SILU; conv_ws_hs_kernel below)
 // NUP = false: a body for convs without up-sampled addends (udp_conv_op.n_up == 0), which then keeps no pixel coordinates
-template <int KS, int STRIDE, int PB, int CP, bool NCHW, bool OUT2 = false, int HS = 0, bool NUP = true>
-__device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile_id, const int cby) {
+// XP: the wave's cout pair is given (`xpair`) instead of following from the cout block and the wave (conv_ws_s2x_kernel)
+template <int KS, int STRIDE, int PB, int CP, bool NCHW, bool OUT2 = false, int HS = 0, bool NUP = true, bool XP = false>
+__device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile_id, const int cby, const int xpair = 0) {
   using T = H2;
   constexpr int CK = 32, ESZ = 2, NB = 2, NW = 4;
   constexpr int PAD = KS / 2, TAPS = KS * KS;
@@ -105,13 +106,14 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   const __amdgpu_buffer_rsrc_t r_res = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(p.res), 0, (p.res && !dbg_nores) ? out_pix * respb : 0, 0x00020000);
 
-  const int cwave = (cby * CP + cp) * 32;   // first cout of the wave's pair of blocks
+  const int pair = XP ? xpair : cby * CP + cp;
+  const int cwave = pair * 32;              // first cout of the wave's pair of blocks
   const int cbase = cwave + 8 * kg;                // the lane's 8 consecutive output channels
   // ---- weights (fragment-major, udp_conv_op.wfmt == 1): the 1 KiB block (tap, chunk, cout pair, nb, plane) holds
   // lane l's 8 K values at 16*l -- A-fragment row li of block nb is cout cwave + 8*(li>>2) + 4*nb + (li&3), so
   // that a lane ends up with 8 consecutive couts.  One contiguous load per fragment; cin is zero-padded.
   const unsigned wvoff = (unsigned)lane * 16u;
-  const unsigned wpair = (unsigned)(cby * CP + cp) * 4096u;
+  const unsigned wpair = (unsigned)pair * 4096u;
   // A fragments of one tap (2 blocks x hi/lo = 16 registers) in a ring of three: the fragments of step s + 2
   // stream in from L2 while step s feeds the MFMAs (step = one tap of one K chunk)
   constexpr int AD = UDP_WS_AD;          // depth of the A ring (fragments of step s + AD - 1 are in flight)
@@ -555,6 +557,82 @@ __global__ __launch_bounds__(256, 2) void conv_ws_pb8_kernel(const ConvParams p)
   conv_ws_body<3, 1, 8, 1, false, false, 0, false>(p, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Shared-input launch of an exchange unit (hrnet.hip, mark_x0_share): the branch-0 map x0 (32 channels, the largest map
+// of its stage) is read by up to three 3x3 stride-2 convs (fuse_layers.i.0.0: 32 -> 64 | 32 | 32) and by the unit's
+// element-wise output 0 (fuse0: relu(x0 + up-sampled addends)).  The convs have one geometry and one K chunk, so ONE
+// staged halo tile serves all their cout pairs: a workgroup = CP cout-pair slots, slot s runs the unchanged body with
+// the weights / bias / residual / addends / output view of its route (ConvShare::route, ::lpair; wave-uniform).  A slot
+// without a route (three pairs under CP = 4) runs the body with a pair index far past its route's last pair: every
+// load of it is out of its descriptor's range (zeros) or masked and every store dropped; it takes the barriers and
+// stages its share of the tile like any other wave.
+//
+// Side output: with its halo cut off, the stride-2 tile is exactly the 2R x 2TW patch of x0 under the tile's output
+// pixels -- input rows 1..2R, columns 1..2TW of the staged tile -- and these patches partition the map.  After the
+// convs' epilogue (one K chunk: the tile is still resident and nothing writes LDS again, so no barrier is needed) the
+// workgroup reads the patch back from LDS and writes fuse0's output for it, in fuse_sum_kernel's operation order.
+__device__ __forceinline__ void s2x_side(const ConvParams& p, const ConvParams& f, const int tile_id) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int t = tile_id;   // the body's tile decode
+  const int tx = t % p.tiles_x;
+  t /= p.tiles_x;
+  const int ty = t % p.tiles_y;
+  const int n0 = (t / p.tiles_y) * p.G;
+  const int IH = p.IH, IW = p.IW;
+  const int in_bytes = ((p.G * IH * IW + 15) >> 4) * 16 * ROWB;
+  const int PW = 2 * p.TW, PHW = 2 * p.R * PW;       // the patch of one image
+  const int gy0 = 2 * ty * p.R, gx0 = 2 * tx * p.TW;
+  const int items = p.G * PHW * 4;                   // 16-byte parts: four consecutive lanes write one pixel's 64 bytes per plane
+  const unsigned outpb = (unsigned)f.out_pitch * 4u, out_lo = (unsigned)f.out_pitch * 2u;
+  const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(f.out, 0, (unsigned)f.N * f.Hout * f.Wout * outpb, 0x00020000);
+  for (int it = threadIdx.x; it < items; it += 256) {
+    const int part = it & 3, pp = it >> 2;
+    const int g = fdiv20(pp, f.mRT);
+    const int rem = pp - g * PHW;
+    const int r = fdiv20(rem, f.mTW);
+    const int x = rem - r * PW;
+    const int n = n0 + g, gy = gy0 + r, gx = gx0 + x;
+    if (n >= p.N || gy >= p.Hin || gx >= p.Win) continue;
+    const int row = (g * IH + r + 1) * IW + x + 1;
+    const unsigned char* q = smem + row * ROWB + ((part ^ swz<H2>(row)) << 4);
+    const f16x8 hi = *reinterpret_cast<const f16x8*>(q), lo = *reinterpret_cast<const f16x8*>(q + in_bytes);
+    f32x4 v[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[0][k] = (float)hi[k] + (float)lo[k] * kLoInv;
+      v[1][k] = (float)hi[4 + k] + (float)lo[4 + k] * kLoInv;
+    }
+    const int c = 8 * part;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      if (u < f.nup) {
+        const int sh = f.up_shift[u];
+        const size_t up_pix = ((size_t)(n * (f.Hout >> sh) + (gy >> sh)) * (f.Wout >> sh) + (gx >> sh));
+        add_vec<H2, 2>(v, reinterpret_cast<const unsigned char*>(f.up[u]) + (up_pix * f.Cout * 2 + c) * 2, f.Cout * 2);
+      }
+    }
+    if (f.relu) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[0][k] = v[0][k] > 0.f ? v[0][k] : 0.f;
+        v[1][k] = v[1][k] > 0.f ? v[1][k] : 0.f;
+      }
+    }
+    const unsigned pix = __umul24(__umul24(n, p.Hin) + gy, p.Win) + gx;
+    store_vec_buf<H2, 2>(r_out, pix * outpb + (unsigned)(f.out_coff + c) * 2u, out_lo, v);
+  }
+}
+
+template <int PB, int CP>
+__global__ __launch_bounds__(256, 2) void conv_ws_s2x_kernel(const ConvShare m) {
+  // (readfirstlane: see conv_ws_multi -- the route's fields are wave-uniform)
+  const int slot = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) % CP;
+  const int r = __builtin_amdgcn_readfirstlane((int)((m.route >> (8 * slot)) & 255u));
+  const int lp = __builtin_amdgcn_readfirstlane((int)((m.lpair >> (8 * slot)) & 255u));
+  conv_ws_body<3, 2, PB, CP, false, false, 0, true, true>(m.p[r], (int)blockIdx.x, 0, lp);
+  if (m.side.out) s2x_side(m.p[0], m.side, (int)blockIdx.x);
+}
+
 // Weight-stationary split-fp16 conv (conv_ws_h2_kernel): tile choice + dispatch.  Returns 1 when the
 // shape does not qualify (the caller falls back to conv_mfma_kernel<H2>).
 template <int KS, int STRIDE, int PB, int CP, bool NCHW>
@@ -774,6 +852,120 @@ int describe_conv_ws(ConvParams p, int ks, int stride, Launch* out, bool grouped
     out->ws_cp = best.cp;
   }
   return rc;
+}
+
+template <int PB, int CP>
+static int describe_s2x_one(size_t lds, int ntiles, Launch* out) {
+  static bool attr_set = false;
+  const void* kern = reinterpret_cast<const void*>(&conv_ws_s2x_kernel<PB, CP>);
+  if (!attr_set) {
+    UDP_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  out->fn = kern;
+  out->grid = dim3(ntiles);
+  out->block = dim3(256);
+  out->lds = (unsigned)lds;
+  return UDP_OK;
+}
+
+// Tile of the shared-input launch: every cout pair of every route under one workgroup (cp slots), the fattest wave tile
+// that still fills the chip (choose_conv_ws's rule), within the 80 KB that leave room for a second workgroup on the CU.
+// Host arithmetic only.  false: no such tile.
+static bool choose_share_tile(const ConvParams& c0, int cp, WsTile* best) {
+  ConvParams q = c0;
+  q.Cout = q.CoutPad = cp * 32;
+  const char* v = getenv("UDP_POSE_WS_MINWGS");
+  const long min_wgs = v ? atol(v) : g_ws_fill_wgs;
+  WsTile t{};
+  bool have = false;
+  for (int pb : {6, 4, 3, 2}) {
+    if (!ws_tile(q, 3, 2, cp, pb, &t, false) || t.lds > 80 * 1024 || t.sbuf) continue;
+    const bool fills = t.wgs >= min_wgs, best_fills = have && best->wgs >= min_wgs;
+    if (!have || (!best_fills && (fills || t.wgs > best->wgs))) {
+      *best = t;
+      have = true;
+    }
+  }
+  return have;
+}
+
+// convs[0..n): UDP_OP_CONVs as describe_all resolved them (3x3 stride 2, Cin = 32, the same input view); `fuse`: the
+// UDP_OP_FUSE over that view, or null.  Returns 1 when there is no kernel for the set (the caller keeps its launches).
+int describe_x0_share(const ConvParams* convs, int n, const ConvParams* fuse, const char* tag, Launch* out) {
+  if (n < 1 || n > kShareRoutes) return 1;
+  const ConvParams& c0 = convs[0];
+  int pairs = 0;
+  for (int j = 0; j < n; ++j) {
+    const ConvParams& c = convs[j];
+    if (c.Cin != 32 || c.wfmt != 1 || c.out_nchw_f32 || c.nout2 || c.in_stuff2 || c.bn_ws || c.relu > UDP_ACT_RELU || !c.out || c.in != c0.in ||
+        c.in_pitch != c0.in_pitch || c.in_coff != c0.in_coff || c.N != c0.N || c.Hin != c0.Hin || c.Win != c0.Win || c.Hout != c0.Hout ||
+        c.Wout != c0.Wout || c.CoutPad % 32 || c.CoutPad / 32 > 4)
+      return 1;
+    pairs += c.CoutPad / 32;
+  }
+  if (pairs > 4 || n + (fuse ? 1 : 0) < 2) return 1;
+  if (fuse && (fuse->in != c0.in || fuse->in_pitch != c0.in_pitch || fuse->in_coff != c0.in_coff || fuse->Cout != 32 || fuse->N != c0.N ||
+               fuse->Hout != c0.Hin || fuse->Wout != c0.Win || fuse->res || !fuse->out || fuse->relu > UDP_ACT_RELU || fuse->out_pitch % 8 ||
+               fuse->out_coff % 8 || (size_t)fuse->N * fuse->Hout * fuse->Wout * fuse->out_pitch * 4 >= 0x7FFF0000u))
+    return 1;
+  const int cp = pairs <= 2 ? 2 : 4;
+  WsTile best{};
+  if (!choose_share_tile(c0, cp, &best)) return 1;
+  auto m = std::make_shared<ConvShare>();
+  memset(m.get(), 0, sizeof(ConvShare));
+  auto magic = [](int d) { return (unsigned)(((1u << 20) + (unsigned)d - 1) / (unsigned)d); };
+  int ntiles = 0;
+  for (int j = 0; j < n; ++j) {
+    ConvParams& p = m->p[j];
+    p = convs[j];
+    p.G = best.G;
+    p.R = best.R;
+    p.TW = best.TW;
+    p.sbuf = 0;
+    p.IH = (p.R - 1) * 2 + 3;
+    p.IW = (p.TW - 1) * 2 + 3;
+    p.tiles_x = ceil_div(p.Wout, p.TW);
+    p.tiles_y = ceil_div(p.Hout, p.R);
+    p.mIW = magic(p.IW);
+    p.mIH = magic(p.IH);
+    p.mRT = magic(p.R * p.TW);
+    p.mTW = magic(p.TW);
+    p.ntiles = ntiles = ceil_div(p.N, p.G) * p.tiles_y * p.tiles_x;
+  }
+  for (int j = n; j < kShareRoutes; ++j) m->p[j] = m->p[0];
+  // slot -> (route, pair in the route); a slot without a route: route 0, pair 255 -- past the weight and bias descriptors at
+  // every tap (<= 4 pairs x 9 taps x 4 KiB), so the wave multiplies zeros and its range check sees zeros
+  int slot = 0;
+  for (int j = 0; j < n; ++j)
+    for (int lp = 0; lp < convs[j].CoutPad / 32; ++lp, ++slot) {
+      m->route |= (unsigned)j << (8 * slot);
+      m->lpair |= (unsigned)lp << (8 * slot);
+    }
+  for (; slot < cp; ++slot) m->lpair |= 255u << (8 * slot);
+  if (fuse) {
+    m->side = *fuse;
+    m->side.mRT = magic(4 * best.R * best.TW);
+    m->side.mTW = magic(2 * best.TW);
+  }
+  int rc = 1;
+#define UDP_S2X(B, C) \
+  if (best.pb == B && cp == C) rc = describe_s2x_one<B, C>(best.lds, ntiles, out);
+  UDP_S2X(2, 2) UDP_S2X(3, 2) UDP_S2X(4, 2) UDP_S2X(6, 2) UDP_S2X(2, 4) UDP_S2X(3, 4) UDP_S2X(4, 4) UDP_S2X(6, 4)
+#undef UDP_S2X
+  if (rc) return rc;
+  out->groupable = 0;
+  out->ws_cp = 0;
+  out->pair = 0;
+  out->p = m->p[0];
+  out->share = m;
+  if (getenv("UDP_POSE_DEBUG_TILES")) {
+    char routes[64] = "";
+    for (int j = 0; j < n; ++j) snprintf(routes + strlen(routes), sizeof(routes) - strlen(routes), "%s%d", j ? "," : "", convs[j].Cout);
+    fprintf(stderr, "x0 share %dx%d C32: %s pairs=%d routes=[%s] fuse0=%d G=%d R=%d TW=%d CP=%d PB=%d lds=%zu wgs=%d\n", c0.Hin, c0.Win, tag ? tag : "",
+            pairs, routes, fuse ? 1 : 0, best.G, best.R, best.TW, cp, best.pb, best.lds, ntiles);
+  }
+  return UDP_OK;
 }
 
 // Dispatch order of a merged weight-stationary launch.  Members arrive deepest-K first: long, matrix-bound

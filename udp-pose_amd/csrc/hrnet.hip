@@ -2,6 +2,7 @@
 // (include/udp_pose_hip.h, udp_conv_op) on one HIP stream, optionally replaying
 // it as a hipGraph.  Replaces PoseHighResolutionNet.forward,
 // deep_hrnet/lib/models/pose_hrnet.py:436-471.
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 
@@ -483,6 +484,164 @@ static int mark_head_chain(const udp_hrnet* h, std::vector<Launch>& L) {
   return UDP_OK;
 }
 
+// Shared-input sets of an exchange unit (conv_ws.hip, conv_ws_s2x_kernel).  The branch-0 map of a unit is read in full
+// by its element-wise output 0 (UDP_OP_FUSE) and by the first stride-2 conv of every chain that leaves branch 0
+// (fuse_layers.i.0.0): one launch at the position of the EARLIEST of them stages each tile once and does the work of
+// all.  A set = 1..3 UDP_OP_CONVs (3x3, stride 2, 32 input channels, fragment-major weights, NHWC output, no chain /
+// second outputs / group; <= 4 cout pairs in all) over one input view, and at most one UDP_OP_FUSE of 32 channels over
+// that view; two members at least.
+//
+// A later member runs earlier than the planner placed it, and the planner gave it buffers by lifetime at its own index
+// (program.py, _assign_buffers), so every candidate k is checked on the buffer ids (and channel slices), against the launch position e:
+//   * an op strictly between e and k that is not a member touches none of k's outputs and writes none of k's inputs
+//     (input, residual, addends),
+//   * no buffer k writes is read or written by another member, and no member writes what k reads (they run side by
+//     side in one launch),
+//   * k waits for nothing that comes after e.
+// A candidate that fails is left out; it keeps its own launch.
+// Lanes: the planner puts an op on the lane of its output's resolution, so the sum and the convs of a set sit on
+// different lanes, and a lane orders its own ops without listing them as waits.  A program with such a set therefore
+// runs as ONE chain in program order, as a program with merged launch groups does (make_nodes, `grouped`) -- the
+// grouped split-fp16 programs are one chain already; members of one lane keep the lanes, the carrying launch then
+// takes the carried ops' waits and records their signals (enqueue_all, build_graph).
+struct ShareSet {
+  int first = -1;            // the carrying op (earliest member)
+  int fuse = -1;             // the UDP_OP_FUSE member, or -1
+  int conv[kShareRoutes];    // the conv members, in program order
+  int n = 0;
+};
+// Channel slice [lo, hi) of the buffer's pixels of `pitch` channels; pitch 0: the whole buffer (addends, and every
+// operand of the op kinds whose fields are not plain channel views).  Slices of one buffer with one pitch and disjoint
+// channel ranges share no byte, whatever the map sizes are (a concat tensor written in slices, hrnet_plan.py `cat`).
+struct BufView {
+  int buf, lo, hi, pitch;
+};
+static bool views_meet(const BufView& a, const BufView& b) {
+  return a.buf == b.buf && (a.pitch == 0 || a.pitch != b.pitch || (a.lo < b.hi && b.lo < a.hi));
+}
+static void op_views(const udp_conv_op& o, std::vector<BufView>& reads, std::vector<BufView>& writes) {
+  reads.clear();
+  writes.clear();
+  const bool plain = o.kind == UDP_OP_CONV || o.kind == UDP_OP_FUSE;
+  auto put = [&](std::vector<BufView>& v, int b, int coff, int c, int pitch) {
+    if (b >= 0) v.push_back(plain ? BufView{b, coff, coff + c, pitch ? pitch : c} : BufView{b, 0, 0, 0});
+  };
+  put(reads, o.in_buf, o.in_coff, o.cin, o.in_pitch);
+  put(reads, o.res_buf, o.res_coff, o.cout, o.res_pitch);
+  for (int u = 0; u < o.n_up && u < 3; ++u) reads.push_back(BufView{o.up_buf[u], 0, 0, 0});
+  for (int u = 0; u < o.n_out2 && u < 2; ++u) put(reads, o.add2_buf[u], o.add2_coff[u], o.cout, o.add2_pitch[u]);
+  put(writes, o.out_buf, o.out_coff, o.cout, o.out_pitch);
+  for (int u = 0; u < o.n_out2 && u < 2; ++u) put(writes, o.out2_buf[u], o.out2_coff[u], o.cout, o.out2_pitch[u]);
+  if (o.chain_cout && o.chain_buf >= 0) writes.push_back(BufView{o.chain_buf, 0, 0, 0});
+}
+static bool meet(const std::vector<BufView>& a, const std::vector<BufView>& b) {
+  for (const BufView& x : a)
+    for (const BufView& y : b)
+      if (views_meet(x, y)) return true;
+  return false;
+}
+static bool meet2(const std::vector<BufView>& a, const std::vector<BufView>& b, const std::vector<BufView>& c) { return meet(a, b) || meet(a, c); }
+static std::vector<ShareSet> find_share_sets(const std::vector<udp_conv_op>& ops) {
+  auto conv_ok = [](const udp_conv_op& o) {
+    return o.kind == UDP_OP_CONV && o.ks == 3 && o.stride == 2 && o.cin == 32 && o.wfmt == 1 && !o.chain_cout && !o.n_out2 && !o.in_stuff2 &&
+           !o.group && o.in_buf >= 0 && o.out_buf >= 0 && o.cout_pad >= 32 && o.cout_pad % 32 == 0 && o.cout_pad <= 128 && o.relu <= UDP_ACT_RELU;
+  };
+  auto fuse_ok = [](const udp_conv_op& o) {
+    return o.kind == UDP_OP_FUSE && o.cin == 32 && o.cout == 32 && o.res_buf == UDP_BUF_NONE && o.in_buf >= 0 && o.out_buf >= 0 && o.relu <= UDP_ACT_RELU;
+  };
+  auto same_view = [](const udp_conv_op& a, const udp_conv_op& b) {
+    return a.in_buf == b.in_buf && a.in_coff == b.in_coff && (a.in_pitch ? a.in_pitch : a.cin) == (b.in_pitch ? b.in_pitch : b.cin) &&
+           a.hin == b.hin && a.win == b.win;
+  };
+  const int n_ops = (int)ops.size();
+  std::vector<char> used(ops.size(), 0);
+  std::vector<ShareSet> sets;
+  std::vector<BufView> rk, wk, ro, wo;
+  for (int e = 0; e < n_ops; ++e) {
+    if (used[e] || !(conv_ok(ops[e]) || fuse_ok(ops[e]))) continue;
+    ShareSet s;
+    s.first = e;
+    int pairs = 0;
+    std::vector<int> members;
+    auto take = [&](int k) {
+      if (ops[k].kind == UDP_OP_FUSE) {
+        s.fuse = k;
+      } else {
+        s.conv[s.n++] = k;
+        pairs += ops[k].cout_pad / 32;
+      }
+      members.push_back(k);
+    };
+    take(e);
+    for (int k = e + 1; k < n_ops; ++k) {
+      const udp_conv_op& c = ops[k];
+      op_views(c, rk, wk);
+      op_views(ops[e], ro, wo);
+      if (meet(wk, std::vector<BufView>(1, ro[0]))) break;   // the view holds another tensor from here on
+      if (used[k] || !same_view(c, ops[e])) continue;
+      if (fuse_ok(c) ? s.fuse >= 0 : !conv_ok(c) || s.n == kShareRoutes || pairs + c.cout_pad / 32 > 4) continue;
+      bool ok = true;
+      for (int w = 0; w < c.n_wait && ok; ++w) ok = c.wait_op[w] < e;
+      // (one rule for both kinds of op in [e, k): a member there runs beside k, any other op now runs after k)
+      for (int i = e; i < k && ok; ++i) {
+        op_views(ops[i], ro, wo);
+        ok = !meet2(wk, ro, wo) && !meet(wo, rk);
+      }
+      if (ok) take(k);
+    }
+    if (members.size() < 2 || s.n < 1) continue;
+    for (int k : members) used[k] = 1;
+    sets.push_back(s);
+  }
+  return sets;
+}
+
+// Diagnostic (tests/test_x0_share_cpu.py, no GPU needed): the shared-input sets of an op list.  carrier[i] = the op whose
+// launch does op i's work (i itself for the carrying op of a set), -1 for an op outside every set.  Returns the number
+// of sets, or -1.
+extern "C" int udp_debug_x0_share(const udp_conv_op* ops, int n_ops, int* carrier) {
+  if (!ops || n_ops < 1 || !carrier) return -1;
+  for (int i = 0; i < n_ops; ++i) carrier[i] = -1;
+  const std::vector<ShareSet> sets = find_share_sets(std::vector<udp_conv_op>(ops, ops + n_ops));
+  for (const ShareSet& s : sets) {
+    if (s.fuse >= 0) carrier[s.fuse] = s.first;
+    for (int j = 0; j < s.n; ++j) carrier[s.conv[j]] = s.first;
+  }
+  return (int)sets.size();
+}
+
+// UDP_POSE_NO_X0_SHARE=1 keeps every member's own launch (read per describe, as UDP_POSE_NO_HEAD_CHAIN is).
+static int mark_x0_share(const udp_hrnet* h, std::vector<Launch>& L) {
+  const char* off = getenv("UDP_POSE_NO_X0_SHARE");
+  if (h->dtype != UDP_F16X2 || (off && atoi(off) != 0)) return UDP_OK;
+  for (const ShareSet& s : find_share_sets(h->ops)) {
+    ConvParams convs[kShareRoutes];
+    char tag[96] = "ops ";
+    auto name = [&](int k) { snprintf(tag + strlen(tag), sizeof(tag) - strlen(tag), "%s%d", strlen(tag) > 4 ? "+" : "", k); };
+    if (s.fuse >= 0 && s.fuse < s.conv[0]) name(s.fuse);
+    for (int j = 0; j < s.n; ++j) {
+      convs[j] = L[s.conv[j]].p;
+      name(s.conv[j]);
+    }
+    if (s.fuse > s.conv[0]) name(s.fuse);
+    Launch fused;
+    const int rc = describe_x0_share(convs, s.n, s.fuse >= 0 ? &L[s.fuse].p : nullptr, tag, &fused);
+    if (rc == 1) continue;       // no kernel for this set
+    if (rc) return rc;
+    auto carry = [&](int k) {
+      if (k < 0 || k == s.first) return;
+      fused.carry[fused.n_carry++] = k;
+      fused.cross_lane |= h->ops[k].lane != h->ops[s.first].lane;
+      L[k] = Launch();
+      L[k].carried = 1;
+    };
+    carry(s.fuse);
+    for (int j = 0; j < s.n; ++j) carry(s.conv[j]);
+    L[s.first] = fused;
+  }
+  return UDP_OK;
+}
+
 // out_skip: ConvParams::out_skip of the ops that write UDP_BUF_OUTPUT (0: the plain [images | mirrored] layout at `out`).
 static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, int out_skip, char* ws, float* out,
                         std::vector<Launch>& ls) {
@@ -600,7 +759,8 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, in
     }
     if (rc) return rc;
   }
-  return mark_head_chain(h, ls);
+  if (const int rc = mark_head_chain(h, ls)) return rc;
+  return mark_x0_share(h, ls);
 }
 
 // Launch list: runs of groupable convs with the same group id become one conv_mfma_multi launch; a chained head pair
@@ -614,6 +774,11 @@ static std::vector<Node> make_nodes(const udp_hrnet* h, const std::vector<Launch
   *grouped = false;
   for (size_t i = 0; i < L.size();) {
     int n = 1;
+    if (L[i].carried) {           // done by an earlier launch (mark_x0_share): no node
+      ++i;
+      continue;
+    }
+    *grouped |= L[i].cross_lane != 0;       // a shared-input launch that carries ops of other lanes: one chain
     if (L[i].pair) {
       n = 2;                      // (both ops on one lane: no reason to give up the lanes, `grouped` stays)
     } else if (L[i].groupable && h->ops[i].group != 0) {
@@ -663,19 +828,26 @@ static int enqueue_all(udp_hrnet* h, const std::vector<Launch>& L, hipStream_t s
     }
   }
   for (size_t i = 0; i < h->ops.size(); ++i) {
+    if (L[i].carried) continue;                       // done by an earlier launch (mark_x0_share)
     const udp_conv_op& o = h->ops[i];
     hipStream_t os = ls[o.lane];
     const size_t last = i + (L[i].pair ? 1 : 0);      // a chained head pair: one launch for ops i and i + 1 (same lane)
+    // the ops of this launch: i (.. last) and the ops it carries -- their waits are honoured here, their signals
+    // recorded behind it (a carried op is on this lane and waits only for ops before i: find_share_sets)
+    size_t mine[2 + kShareRoutes];
+    int n_mine = 0;
+    for (size_t j = i; j <= last; ++j) mine[n_mine++] = j;
+    for (int c = 0; c < L[i].n_carry; ++c) mine[n_mine++] = (size_t)L[i].carry[c];
     if (lanes)
-      for (size_t j = i; j <= last; ++j)
-        for (int k = 0; k < h->ops[j].n_wait; ++k)
-          if (h->ops[h->ops[j].wait_op[k]].lane != o.lane) UDP_HIP_CHECK(hipStreamWaitEvent(os, h->op_done[h->ops[j].wait_op[k]], 0));
+      for (int m = 0; m < n_mine; ++m)
+        for (int k = 0; k < h->ops[mine[m]].n_wait; ++k)
+          if (h->ops[h->ops[mine[m]].wait_op[k]].lane != o.lane) UDP_HIP_CHECK(hipStreamWaitEvent(os, h->op_done[h->ops[mine[m]].wait_op[k]], 0));
     if (ev) UDP_HIP_CHECK(hipEventRecord(ev[2 * i], os));
     const int rc = run_launch(L[i], os);
     if (rc) return rc;
     if (ev) UDP_HIP_CHECK(hipEventRecord(ev[2 * i + 1], os));
-    for (size_t j = i; j <= last; ++j)
-      if (lanes && h->op_signals[j]) UDP_HIP_CHECK(hipEventRecord(h->op_done[j], os));
+    for (int m = 0; m < n_mine; ++m)
+      if (lanes && h->op_signals[mine[m]]) UDP_HIP_CHECK(hipEventRecord(h->op_done[mine[m]], os));
     i = last;
   }
   if (lanes)
@@ -708,6 +880,8 @@ static int build_graph(udp_hrnet* h, const std::vector<Launch>& L, hipGraph_t* g
       for (int j = 0; j < nodes[k].n; ++j)       // (n > 1 here: a chained head pair, whose second op may wait on the first)
         for (int w = 0; w < h->ops[i + j].n_wait; ++w)
           if ((size_t)h->ops[i + j].wait_op[w] < i) deps.push_back(node[node_of_op[h->ops[i + j].wait_op[w]]]);
+      for (int c = 0; c < L[i].n_carry; ++c)     // the ops this launch carries wait for ops before i only (find_share_sets)
+        for (int w = 0; w < h->ops[L[i].carry[c]].n_wait; ++w) deps.push_back(node[node_of_op[h->ops[L[i].carry[c]].wait_op[w]]]);
     }
     ConvParams p = L[i].p;
     ConvMulti m;
@@ -721,6 +895,7 @@ static int build_graph(udp_hrnet* h, const std::vector<Launch>& L, hipGraph_t* g
       }
       args[0] = &m;
     }
+    if (L[i].share) args[0] = L[i].share.get();
     hipKernelNodeParams kp;
     memset(&kp, 0, sizeof(kp));
     kp.func = const_cast<void*>(ml.fn);
@@ -735,6 +910,7 @@ static int build_graph(udp_hrnet* h, const std::vector<Launch>& L, hipGraph_t* g
       return fail(UDP_ERR_HIP, "hipGraphAddKernelNode(op %zu): %s", i, hipGetErrorString(e));
     }
     for (int j = 0; j < nodes[k].n; ++j) node_of_op[i + j] = (int)k;
+    for (int c = 0; c < L[i].n_carry; ++c) node_of_op[L[i].carry[c]] = (int)k;
     last_on_lane[o.lane] = (int)k;
   }
   hipError_t e = hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0);
@@ -778,6 +954,9 @@ extern "C" int udp_hrnet_profile(udp_hrnet* h, const float* in_nchw, int n, int 
   hipError_t se = hipStreamSynchronize(s);
   if (!rc && se == hipSuccess) {
     bool grouped = false;
+    // (an op carried by an earlier launch: 0 -- the whole time is with the carrying op)
+    for (size_t i = 0; i < nops; ++i)
+      if (L[i].carried) ms_per_op[i] = 0.f;
     for (const Node& nd : make_nodes(h, L, &grouped)) {
       float t = -1.f;
       if (hipEventElapsedTime(&t, ev[2 * nd.first], ev[2 * nd.first + 1]) != hipSuccess) t = -1.f;
