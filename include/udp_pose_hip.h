@@ -76,7 +76,15 @@ const char* udp_last_error(void);
  * ------------------------------------------------------------------------- */
 enum udp_op_kind {
   UDP_OP_STEM = 0, /* 3x3 s2 conv, Cin=3, reads the NCHW fp32 network input    */
-  UDP_OP_CONV = 1, /* implicit-GEMM conv on MFMA, ks 1|3, stride 1|2           */
+  UDP_OP_CONV = 1, /* implicit-GEMM conv on MFMA, ks 1|3, stride 1|2; ks 7: stride 1 (below) */
+  /* UDP_OP_CONV with ks = 7 (csrc/conv7.hip; the 7x7 stride-1 64 -> 64 conv of the stem of RSN-18 "se + prm"): stride 1,
+   * pad 3, NHWC in and out, UDP_F32 (v_mfma_f32_16x16x4_f32) and UDP_F16X2 (the three-MFMA split-fp16 product, fp32
+   * accumulation) -- UDP_BF16 is UDP_ERR_UNSUPPORTED.  Weights wfmt 0, [49 taps][cout_pad][cin] (tap = 7 ky + kx), bias
+   * folded, relu 0 | 1.  cin and cout multiples of 16; in_coff / in_pitch / out_coff / out_pitch are honoured under the
+   * 16-byte rule of every UDP_OP_CONV.  Pixels outside the image contribute exact zeros; a pixel's sum runs in one fixed
+   * order (K chunk, ky, kx) whatever tile or image group it falls into, so results do not depend on the batch.  Refused
+   * with UDP_ERR_UNSUPPORTED, never ignored: res, n_up, n_out2, the NCHW output (out_buf = UDP_BUF_OUTPUT), in_stuff2,
+   * an output placed for a sub-batch lane (out_skip), UDP_ACT_HSWISH / UDP_ACT_SILU, chain_cout, group, wfmt 1, stride 2. */
   UDP_OP_FUSE = 2, /* no conv: out = act(in [+ res] + sum_k nearest_up(up_k))  */
   UDP_OP_STEM7 = 3,   /* 7x7 s2 p3 conv, Cin=3, reads the NCHW fp32 network input (RSN top) */
   UDP_OP_MAXPOOL = 4, /* MaxPool2d(3, stride 2, pad 1) */
@@ -315,7 +323,7 @@ enum udp_op_kind {
 
 typedef struct udp_conv_op {
   int32_t kind;            /* enum udp_op_kind */
-  int32_t ks, stride;      /* kernel size 1|3 (UDP_OP_DWCONV: 3|5|7, UDP_OP_PRM_DW9: 9; pad = ks/2; UDP_OP_LINATTN / UDP_OP_MHATTN: 2 = the patch size), stride 1|2 */
+  int32_t ks, stride;      /* kernel size 1|3, UDP_OP_CONV also 7 at stride 1 (see UDP_OP_CONV) (UDP_OP_DWCONV: 3|5|7, UDP_OP_PRM_DW9: 9; pad = ks/2; UDP_OP_LINATTN / UDP_OP_MHATTN: 2 = the patch size), stride 1|2 */
   int32_t relu;            /* activation of the epilogue: UDP_ACT_NONE / UDP_ACT_RELU / UDP_ACT_HSWISH / UDP_ACT_SILU (see there) */
   int32_t cin, cout;       /* real channel counts (cin multiple of 16 for UDP_OP_CONV) */
   int32_t cout_pad;        /* cout rounded up to a multiple of 32: rows of `weights`/`bias` */
@@ -585,7 +593,10 @@ int udp_debug_multi_order(const unsigned* tiles, const unsigned* ncby, const int
  * the LDS-staged chooser, out[0] = NB (16-channel cout blocks per workgroup), out[1] = MBW (pixel blocks per wave).
  * Then out[2..7] = G, R, TW (tile = G images x R rows x TW columns), one stage buffer (0 | 1), dynamic LDS bytes,
  * workgroups; out[8] = grid.x of the persistent bf16 form when that is what runs (every workgroup then strides over
- * ceil(tiles / out[8]) tiles), else 0.  The choosers read UDP_POSE_WS_PB, UDP_POSE_WS_CP, UDP_POSE_MINWGS and
+ * ceil(tiles / out[8]) tiles), else 0.  ks 7 (wfmt 0, stride 1, UDP_F32 | UDP_F16X2; csrc/conv7.hip): out[0] = NB, out[1] =
+ * MBW, out[2..4] = G, R, TW, out[5] = 1 when the input halo tile has ONE LDS buffer (split fp16, or a single K chunk) and
+ * 0 when it has two, out[6] = dynamic LDS bytes (halo buffers + the two buffers of one kernel row of weights),
+ * out[7] = workgroups, out[8] = 0; grouped: 1.  The choosers read UDP_POSE_WS_PB, UDP_POSE_WS_CP, UDP_POSE_MINWGS and
  * UDP_POSE_MAXM at every call, so a test can force an arm around one call.  Returns UDP_OK, 1 when grouped is set and
  * the conv is no member of a merged launch, or the error udp_conv2d_fused would return.  Adds a symbol only:
  * UDP_POSE_ABI_VERSION stays as it is. */

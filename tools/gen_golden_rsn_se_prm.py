@@ -5,10 +5,10 @@ oracle/gen_golden.py; nothing is copied).
 
 The module is ``RSN(cfg)`` of RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py -- its Bottleneck with the SELayer, its
 Upsample_unit with the PRM -- with ONE substitution made here at generation time: ``net.top`` is the ``ResNet_top`` of
-RSN/exps/RSN18.coco/network.py (7x7 s2 conv + max-pool), because the experiment's own stem (network.py:188-203: 3x3 s2,
-7x7 s1 64 -> 64, 3x3 s2) holds a conv that no kernel of this project covers.  Both stems deliver 64 channels at 1/4
-resolution, so everything behind it is the reference's graph unchanged; the price is that the experiment's checkpoints
-do not load.
+RSN/exps/RSN18.coco/network.py (7x7 s2 conv + max-pool): this is the fixture of ``RSN18Hip(se=True, prm=True)`` on the
+default ``stem="pool"``.  Both stems deliver 64 channels at 1/4 resolution, so everything behind it is the reference's
+graph unchanged.  The experiment's own stem (network.py:188-203: 3x3 s2, 7x7 s1 64 -> 64, 3x3 s2; ``stem="conv7"``) has the
+fixture of tools/gen_golden_rsn_se_prm_top.py, made from the module without any substitution.
 
 The .npz holds the module's fp32 output for one synthetic crop (seed 8) at 256x192 and the BatchNorm calibration
 statistics (24 crops, seed 15; running means rounded to fp16 as in bn_calib_rsn18_17.npz) plus ``final.scale``; it holds

@@ -163,6 +163,11 @@ struct WsTile {
 };
 int choose_conv_ws(ConvParams& p, int ks, int stride, bool grouped, WsTile* best);   // its tile choice alone (host arithmetic, no HIP call)
 int describe_ws_multi(const Launch* members, int n, ConvMulti* m, Launch* out);
+// conv7.hip: UDP_OP_CONV with ks = 7 (stride 1, f32 / f16x2): weights streamed through LDS one kernel row at a time
+int describe_conv7(ConvParams p, int dtype, int stride, Launch* out);
+int conv7_refuse(const ConvParams& p, int dtype, int stride);          // the refusals of its contract alone (UDP_OK: none applies)
+size_t conv7_choose_tile(ConvParams& p, int dtype, int* nb_out);       // its tile choice alone (host arithmetic, no HIP call); 0: nothing fits
+int conv7_h2_overflow(hipStream_t s, int reset, int* flag);
 int describe_conv_chain(ConvParams p, Launch* out);   // two 1x1 convs chained through registers (udp_conv_op.chain_cout)
 // a 1x1 conv with up-sampled addends + ReLU chained into the 1x1 conv that writes the net's NCHW fp32 output; 1: no such kernel
 int describe_head_chain(ConvParams p, const ConvParams& p2, Launch* out);

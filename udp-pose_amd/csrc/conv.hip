@@ -1531,6 +1531,7 @@ int describe_conv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
   if (false ||
       p.N >= 2048)
     return fail(UDP_ERR_UNSUPPORTED, "conv tensor exceeds the 2 GiB the 32-bit buffer offsets cover; split the batch");
+  if (ks == 7) return describe_conv7(p, dtype, stride, out);   // conv7.hip: its own kernel, tile choice and refusals
   if (p.in_stuff2 && (dtype == UDP_F16X2 || stride != 1 || (p.Hin & 1) || (p.Win & 1)))
     return fail(UDP_ERR_UNSUPPORTED, "in_stuff2: a stride-1 fp32 / bf16 conv over an even-sized stuffed image");
   if (p.relu >= UDP_ACT_HSWISH && (ks != 1 || stride != 1 || p.out_nchw_f32 || p.res || p.nup || p.nout2 || p.in_stuff2 || p.bn_ws || dtype == UDP_BF16))
@@ -1563,11 +1564,12 @@ int describe_conv(ConvParams p, int dtype, int ks, int stride, Launch* out) {
 
 // Diagnostic (tests/test_conv_arms_cpu.py, no GPU needed): the decision of the two tile choosers for one UDP_OP_CONV
 // without channel views, as describe_conv / describe_conv_grouped would take it -- choose_conv_ws for wfmt 1,
-// conv_choose_tile otherwise.  Host arithmetic only: no kernel is looked up and no HIP call is made.
+// conv_choose_tile otherwise, conv7_choose_tile for ks 7 (stride 1, wfmt 0, f32 / f16x2; everything else is refused as
+// describe_conv refuses it).  Host arithmetic only: no kernel is looked up and no HIP call is made.
 extern "C" int udp_debug_conv_tile(int dtype, int wfmt, int ks, int stride, int n, int hout, int wout, int cin, int cout,
                                    int nchw_out, int grouped, int* out) {
   if (!out || n < 1 || hout < 1 || wout < 1 || cin < 1 || cout < 1) return fail(UDP_ERR_ARG, "udp_debug_conv_tile: bad argument");
-  if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2)) return fail(UDP_ERR_ARG, "udp_debug_conv_tile: ks/stride");
+  if ((ks != 1 && ks != 3 && ks != 7) || (stride != 1 && stride != 2)) return fail(UDP_ERR_ARG, "udp_debug_conv_tile: ks/stride");
   if (dtype != UDP_F32 && dtype != UDP_BF16 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "udp_debug_conv_tile: dtype %d", dtype);
   ConvParams p;
   memset(&p, 0, sizeof(p));
@@ -1585,7 +1587,20 @@ extern "C" int udp_debug_conv_tile(int dtype, int wfmt, int ks, int stride, int 
   if (p.Cin % 16 != 0) return fail(UDP_ERR_UNSUPPORTED, "conv Cin=%d is not a multiple of 16", p.Cin);
   if (!p.out_nchw_f32 && p.Cout % 16 != 0) return fail(UDP_ERR_UNSUPPORTED, "NHWC conv Cout=%d is not a multiple of 16", p.Cout);
   for (int i = 0; i < 9; ++i) out[i] = 0;
-  if (wfmt == 1) {
+  if (ks == 7) {
+    // conv7.hip: out[0] = NB, out[1] = 16-pixel blocks per wave, out[5] = 1 when the halo tile has one LDS buffer (2 otherwise),
+    // out[6] = LDS bytes, out[7] = workgroups, out[8] = 0; a merged launch has no 7x7 member (grouped: 1)
+    if (grouped) return 1;
+    if (const int rc = conv7_refuse(p, dtype, stride)) return rc;
+    int nb = 2;
+    const size_t lds = conv7_choose_tile(p, dtype, &nb);
+    if (!lds) return fail(UDP_ERR_UNSUPPORTED, "7x7 conv: no tile fits the LDS");
+    out[0] = nb;
+    out[1] = ceil_div(ceil_div(p.G * p.R * p.TW, 16), 4);
+    out[5] = p.sbuf;
+    out[6] = (int)lds;
+    out[7] = p.ntiles * (p.CoutPad / (nb * 16));
+  } else if (wfmt == 1) {
     if (dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "wfmt 1 (fragment-major weights) needs UDP_F16X2");
     if (grouped && (stride != 1 || p.out_nchw_f32)) return 1;          // describe_conv_grouped: not a member of a merged launch
     WsTile t{};

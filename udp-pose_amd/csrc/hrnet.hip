@@ -291,6 +291,13 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
       return fail(UDP_ERR_ARG, "op %d: up_shift %d does not divide %dx%d", idx, s, o.hout, o.wout);
     if (!buf_ok(o.up_buf[u], (int64_t)(o.hout >> s) * (o.wout >> s) * o.cout)) return fail(UDP_ERR_ARG, "op %d: up_buf %d", idx, u);
   }
+  if (o.kind == UDP_OP_CONV && o.ks == 7) {
+    // conv7.hip: a plain conv + bias (+ ReLU) over channel views; what it does not do is refused here, not ignored
+    if (h->dtype == UDP_BF16 || o.stride != 1 || o.wfmt != 0 || o.res_buf != UDP_BUF_NONE || o.n_up || o.n_out2 || o.chain_cout || o.group ||
+        o.in_stuff2 || o.out_buf == UDP_BUF_OUTPUT || o.relu > UDP_ACT_RELU || o.cin % 16 || o.cout % 16)
+      return fail(UDP_ERR_UNSUPPORTED, "op %d: a 7x7 conv is stride 1, f32 / f16x2, wfmt 0, cin and cout multiples of 16, NHWC, bias (+ ReLU) only: "
+                  "no residual, addends, second outputs, chain, group or stuffed input", idx);
+  }
   if (o.chain_cout) {
     if (o.kind != UDP_OP_CONV || o.wfmt != 1 || h->dtype != UDP_F16X2 || o.ks != 1 || o.stride != 1 || o.group || o.n_up || o.n_out2 ||
         o.out_buf < 0 || (o.cin != 64 && o.cin != 128) || o.cout != 256 || o.cout_pad != o.cout || o.chain_cout != 64)
@@ -323,6 +330,7 @@ extern "C" int udp_f16x2_overflow(void* stream, int reset) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int flag = 0;
   int rc = conv_h2_overflow(s, reset, &flag);
+  if (!rc) rc = conv7_h2_overflow(s, reset, &flag);
   if (!rc) rc = conv_ws_h2_overflow(s, reset, &flag);
   if (!rc) rc = psa_h2_overflow(s, reset, &flag);
   if (!rc) rc = deconv_h2_overflow(s, reset, &flag);
@@ -1192,7 +1200,9 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (o->cout <= 0 || o->cout_pad < o->cout || o->cout_pad % 32 || o->n_up < 0 || o->n_up > 3)
     return fail(UDP_ERR_ARG, "udp_conv2d_fused: bad cout/cout_pad/n_up");
   if (o->kind == UDP_OP_CONV) {
-    if ((o->ks != 1 && o->ks != 3) || (o->stride != 1 && o->stride != 2)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: ks/stride");
+    if ((o->ks != 1 && o->ks != 3 && o->ks != 7) || (o->stride != 1 && o->stride != 2)) return fail(UDP_ERR_ARG, "udp_conv2d_fused: ks/stride");
+    if (o->ks == 7 && (o->group || o->chain_cout || o->n_out2))
+      return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_fused: a 7x7 conv takes no group, chained conv or second outputs");
     const int pad = o->ks / 2;
     if (o->hout != (o->hin + 2 * pad - o->ks) / o->stride + 1 || o->wout != (o->win + 2 * pad - o->ks) / o->stride + 1)
       return fail(UDP_ERR_ARG, "udp_conv2d_fused: output size does not match input/stride");

@@ -311,28 +311,56 @@ class RSN18Hip(PoseNetHip):
     """RSN-18 (RSN/exps/RSN18.coco/network.py, STAGE_NUM = 1) inference through the same C ABI;
     ``state_dict`` in the reference module's key format; returns ``outputs[-1][-1]`` ([N,C,H/4,W/4]).
     ``se`` / ``prm``: the SELayer in every Bottleneck and the Pose Refine Machine on the finest level, as in
-    RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py, on this net's stem (rsn_plan.py says why that experiment's own
-    checkpoints do not load); storage modes f32 and f16x2."""
+    RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py.  ``stem``: ``"pool"`` is RSN18.coco's ResNet_top (7x7 s2 conv +
+    max-pool), ``"conv7"`` that experiment's own (3x3 s2, 7x7 s1 64 -> 64, 3x3 s2; keys ``top.conv.{0,1,2}.*``):
+    ``RSN18Hip(17, dtype, se=True, prm=True, stem="conv7")`` loads that experiment's checkpoints as they are, and
+    ``RSN18Hip.from_state_dict(sd)`` reads all of this off a checkpoint.  se, prm and the conv7 stem run in the storage
+    modes f32 and f16x2; bf16 is outside their contract."""
 
     NAME = "RSN-18"
 
-    def __init__(self, out_channels=17, dtype="f32", chl_num=256, se=False, prm=False):
+    def __init__(self, out_channels=17, dtype="f32", chl_num=256, se=False, prm=False, stem="pool"):
+        if stem not in ("pool", "conv7"):
+            raise ValueError("RSN-18 stem must be 'pool' or 'conv7' (got %r)" % (stem,))
         if (se or prm) and dtype not in ("f32", "f16x2"):
             raise ValueError("RSN-18 with se / prm: storage modes 'f32' and 'f16x2' only (got %r)" % (dtype,))
+        if stem == "conv7" and dtype not in ("f32", "f16x2"):
+            raise ValueError("RSN-18 with the conv7 stem: storage modes 'f32' and 'f16x2' only (got %r)" % (dtype,))
         super().__init__(None, dtype)
         self.out_channels = int(out_channels)
         self.chl_num = chl_num
         self.se, self.prm = bool(se), bool(prm)
+        self.stem = stem
+
+    @classmethod
+    def from_state_dict(cls, state_dict, dtype="f32"):
+        """The loaded model for a checkpoint of either experiment, its flags read off the keys and shapes: ``stem`` from
+        ``top.conv.1.conv.weight`` ([64,64,7,7]: "conv7"; absent: "pool"), ``se`` from ``*.se.fc.0.weight``, ``prm`` from
+        ``*.prm.*``, ``out_channels`` and ``chl_num`` from the head conv ``stage0.upsample.up4.res_conv2``.  The strict
+        load that follows refuses whatever else does not fit."""
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        head = "stage0.upsample.up4.res_conv2.conv.weight"
+        if head not in sd or len(sd[head].shape) != 4:
+            raise ValueError("not an RSN-18 state_dict: no %s" % head)
+        top1 = sd.get("top.conv.1.conv.weight")
+        if top1 is not None and tuple(top1.shape) != (64, 64, 7, 7):
+            raise ValueError("top.conv.1.conv.weight must be [64, 64, 7, 7], got %s" % (list(top1.shape),))
+        if top1 is None and "top.conv.conv.weight" not in sd:
+            raise ValueError("not an RSN-18 state_dict: neither top.conv.conv.weight nor top.conv.1.conv.weight")
+        net = cls(int(sd[head].shape[0]), dtype, chl_num=int(sd[head].shape[1]),
+                  se=any(k.endswith(".se.fc.0.weight") for k in sd), prm=any(".prm." in k for k in sd),
+                  stem="pool" if top1 is None else "conv7")
+        return net.load_state_dict(sd, strict=True)
 
     def param_shapes(self):
         from .synth import rsn18_param_shapes, rsn18_se_prm_param_shapes
-        if self.se or self.prm:
-            return rsn18_se_prm_param_shapes(self.out_channels, self.chl_num, self.se, self.prm)
+        if self.se or self.prm or self.stem != "pool":
+            return rsn18_se_prm_param_shapes(self.out_channels, self.chl_num, self.se, self.prm, self.stem)
         return rsn18_param_shapes(self.out_channels, self.chl_num)
 
     def _make_program(self, h, w):
         from .rsn_plan import RSNProgram
-        return RSNProgram(self._sd, h, w, self.dtype, self.chl_num, self.se, self.prm)
+        return RSNProgram(self._sd, h, w, self.dtype, self.chl_num, self.se, self.prm, self.stem)
 
 
 def get_pose_net(cfg, is_train, **kwargs):

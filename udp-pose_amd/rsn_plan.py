@@ -12,12 +12,16 @@ closing 1x1 conv's weight columns are scattered to the padded positions with zer
 3x3 convs read / write channel slices in place, and the pad channels stay exactly 0 (zero weights,
 zero bias, ReLU).  The ``a + b`` that precedes most 3x3 convs is one element-wise launch.
 
-``se`` / ``prm``: the two additions of RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py, on THIS stem (that
-experiment's own ResNet_top, :188-203, holds a 7x7 stride-1 64 -> 64 conv that no kernel here covers: its checkpoints
-do not load).  ``se``: conv_bn_relu3 runs without residual and ReLU, and one UDP_OP_SE_RES launch follows in place with
+``se`` / ``prm``: the two additions of RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py.  ``se``: conv_bn_relu3 runs without residual and ReLU, and one UDP_OP_SE_RES launch follows in place with
 the shortcut as ``res`` and the ReLU on (:51-66, :135-143) -- 16 launches.  ``prm``: behind up4's ReLU the Pose Refine
 Machine (:267-301, :357-358) as 3x3 conv, UDP_OP_PRM_GATE, 1x1 conv, UDP_OP_PRM_DW9 -- 4 launches; res_conv1 reads the
 result.  Both need f32 / f16x2 storage.
+
+``stem``: ``"pool"`` is the ResNet_top above; ``"conv7"`` is that experiment's own ResNet_top (:188-203) -- UDP_OP_STEM
+for ``top.conv.0`` (3x3 s2, 3 -> 64, from the NCHW input, mirrored half included), the 7x7 stride-1 64 -> 64 conv
+``top.conv.1`` at half resolution (UDP_OP_CONV with ks = 7, csrc/conv7.hip), the 3x3 s2 conv ``top.conv.2``, no max-pool:
+3 launches instead of 2, 2.5 GMAC per 256x192 image more.  It goes with or without se / prm and needs f32 / f16x2
+storage as well (the 7x7 conv has no bf16 form); with se + prm the program takes the experiment's own checkpoints.
 """
 import os
 
@@ -28,11 +32,16 @@ from .program import Program, _round_up, storage_bytes
 
 
 class RSNProgram(Program):
-    def __init__(self, state_dict, in_h, in_w, dtype="f32", chl_num=256, se=False, prm=False):
+    def __init__(self, state_dict, in_h, in_w, dtype="f32", chl_num=256, se=False, prm=False, stem="pool"):
         self.chl_num = chl_num
         self.se, self.prm = bool(se), bool(prm)
+        if stem not in ("pool", "conv7"):
+            raise ValueError("RSN-18 stem must be 'pool' or 'conv7' (got %r)" % (stem,))
+        self.stem = stem
         if (self.se or self.prm) and dtype not in ("f32", "f16x2"):
             raise ValueError("RSN-18 with se / prm: storage modes 'f32' and 'f16x2' only (got %r)" % (dtype,))
+        if stem == "conv7" and dtype not in ("f32", "f16x2"):
+            raise ValueError("RSN-18 with the conv7 stem: storage modes 'f32' and 'f16x2' only (got %r)" % (dtype,))
         super().__init__(state_dict, in_h, in_w, dtype)
 
     def _fold_cbr(self, name):
@@ -166,10 +175,17 @@ class RSNProgram(Program):
 
     def _build(self):
         H, W = self.in_h, self.in_w
-        x = self._stem(_lib.UDP_OP_STEM7, "top.conv.conv", "top.conv.bn", 7, name="top.conv")
-        pooled = self._new(64, H // 4, W // 4)
-        self._op(_lib.UDP_OP_MAXPOOL, x, pooled, "top.maxpool", ks=3, stride=2)
-        x = pooled
+        if self.stem == "conv7":
+            x = self._stem(_lib.UDP_OP_STEM, "top.conv.0.conv", "top.conv.0.bn", 3, name="top.conv.0")
+            if tuple(self.sd["top.conv.1.conv.weight"].shape) != (64, 64, 7, 7) or tuple(self.sd["top.conv.2.conv.weight"].shape) != (64, 64, 3, 3):
+                raise ValueError("top.conv.1 / top.conv.2 conv weights must be [64,64,7,7] / [64,64,3,3]")
+            x = self._conv_v(x, "top.conv.1")
+            x = self._conv_v(x, "top.conv.2", stride=2)
+        else:
+            x = self._stem(_lib.UDP_OP_STEM7, "top.conv.conv", "top.conv.bn", 7, name="top.conv")
+            pooled = self._new(64, H // 4, W // 4)
+            self._op(_lib.UDP_OP_MAXPOOL, x, pooled, "top.maxpool", ks=3, stride=2)
+            x = pooled
         feats = []
         for layer, planes in zip(range(1, 5), (64, 128, 256, 512)):
             for blk in range(2):

@@ -348,15 +348,28 @@ def synth_rsn18_state_dict(out_channels=17, seed=0, bn_calib=None):
     return sd
 
 
-def rsn18_se_prm_param_shapes(out_channels=17, chl_num=256, se=True, prm=True):
+def _rsn_top(s, stem):
+    """The keys of ``top``: RSN18.coco's ResNet_top ("pool": 7x7 s2 conv, then a max-pool) or the one of
+    RSN18.coco.e1.se.36x8x132000_prm (network.py:188-203, "conv7": a Sequential of 3x3 s2 3 -> 64, 7x7 s1 64 -> 64, 3x3 s2 64 -> 64)."""
+    if stem == "pool":
+        _cbr(s, "top.conv", 3, 64, 7)
+    elif stem == "conv7":
+        _cbr(s, "top.conv.0", 3, 64, 3)
+        _cbr(s, "top.conv.1", 64, 64, 7)
+        _cbr(s, "top.conv.2", 64, 64, 3)
+    else:
+        raise ValueError("RSN-18 stem must be 'pool' or 'conv7' (got %r)" % (stem,))
+
+
+def rsn18_se_prm_param_shapes(out_channels=17, chl_num=256, se=True, prm=True, stem="pool"):
     """Ordered {key: shape} of the RSN-18 above with the Bottleneck of
     RSN/exps/RSN18.coco.e1.se.36x8x132000_prm/network.py (``se``) and the Pose Refine Machine of its up4 (``prm``), in the
     module's registration order.  That Bottleneck (:68-117) closes with ``se.fc.{0,2}`` (registered behind conv_bn_relu3,
     before downsample) and takes its branch width from ``planes`` (planes * 26 // 64, :74), not from ``in_planes`` as
     RSN18.coco's does: the first block of layers 2 - 4 is twice as wide inside.  ``prm`` is registered last in up4
-    (:337-345)."""
+    (:337-345).  ``stem="conv7"``: with that experiment's own ResNet_top (``_rsn_top``) -- with se and prm, its full key set."""
     s = OrderedDict()
-    _cbr(s, "top.conv", 3, 64, 7)
+    _rsn_top(s, stem)
     in_planes = 64
     for layer, planes in zip(range(1, 5), (64, 128, 256, 512)):
         for b in range(2):
@@ -387,12 +400,14 @@ def rsn18_se_prm_param_shapes(out_channels=17, chl_num=256, se=True, prm=True):
     return s
 
 
-def synth_rsn18_se_prm_state_dict(out_channels=17, seed=0, bn_calib=None, se=True, prm=True):
+def synth_rsn18_se_prm_state_dict(out_channels=17, seed=0, bn_calib=None, se=True, prm=True, stem="pool"):
     """The rules of synth_rsn18_state_dict on the keys above, plus: fc.0 weights N(0, 400 / fan_in) -- the pooled vector it sees is the closing
-    BatchNorm's bias, of order 0.05 -- and fc.2 weights N(0, 4 / fan_in), so that the SE gates spread over (0, 1); PRM BatchNorm weights in [0.8, 1.6] (the two gates see pre-activations of order 1)."""
+    BatchNorm's bias, of order 0.05 -- and fc.2 weights N(0, 4 / fan_in), so that the SE gates spread over (0, 1); PRM BatchNorm weights in [0.8, 1.6] (the two gates see pre-activations of order 1).
+    ``stem="conv7"``: the three stem convs of the experiment's own ResNet_top by the rule of every other conv (He scale); the
+    default draws exactly the tensors it drew before the argument existed."""
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = OrderedDict()
-    for name, shape in rsn18_se_prm_param_shapes(out_channels, 256, se, prm).items():
+    for name, shape in rsn18_se_prm_param_shapes(out_channels, 256, se, prm, stem).items():
         if name.endswith("num_batches_tracked"):
             sd[name] = torch.tensor(0, dtype=torch.long)
             continue
