@@ -599,7 +599,15 @@ int udp_debug_multi_order(const unsigned* tiles, const unsigned* ncby, const int
  * out[7] = workgroups, out[8] = 0; grouped: 1.  The choosers read UDP_POSE_WS_PB, UDP_POSE_WS_CP, UDP_POSE_MINWGS and
  * UDP_POSE_MAXM at every call, so a test can force an arm around one call.  Returns UDP_OK, 1 when grouped is set and
  * the conv is no member of a merged launch, or the error udp_conv2d_fused would return.  Adds a symbol only:
- * UDP_POSE_ABI_VERSION stays as it is. */
+ * UDP_POSE_ABI_VERSION stays as it is.
+ * With UDP_POSE_DEBUG_TILES set, describing a conv prints the same decision to stderr, one line per conv ("ws conv k..",
+ * "conv k..", "grouped conv ..", "x0 share .."), and every merged launch of a program adds one line when it is described
+ * (at every eager forward and when a graph is built):
+ *   ws multi k<3|1>: members=<n> wgs=<workgroups> codes=[c0,..] dispatch=<table|search>
+ *   lds multi <bf16|f16x2> k<3|1>: members=<n> wgs=<workgroups> codes=[m0,..] MBW=<3|4>
+ * codes of "ws multi": each member's kernel variant in launch order (CP 1, 2 or 4; 8 = the 8-pixel-block arm); dispatch: whether
+ * the kernel resolves a workgroup through the per-8 lookup table or the segment search.  codes of "lds multi": the MBW each
+ * member was described for; MBW: that of the conv_mfma_multi instantiation that runs them all (the largest). */
 int udp_debug_conv_tile(int dtype, int wfmt, int ks, int stride, int n, int hout, int wout, int cin, int cout,
                         int nchw_out, int grouped, int* out);
 /* Diagnostic, host only (no GPU, no HIP call): the shared-input sets the executor forms over an op list in UDP_F16X2

@@ -1715,6 +1715,11 @@ int describe_multi(const Launch* members, int n, ConvMulti* m, Launch* out) {
   }
   for (int j = n; j < 5; ++j) m->start[j] = j < 4 ? 0xFFFFFFFFu : total;
   for (int j = n; j < 4; ++j) m->tiles[j] = 1;
+  if (getenv("UDP_POSE_DEBUG_TILES")) {
+    char codes[64] = "";
+    for (int j = 0; j < n; ++j) snprintf(codes + strlen(codes), sizeof(codes) - strlen(codes), "%s%d", j ? "," : "", members[j].groupable % 10);
+    fprintf(stderr, "lds multi %s k%d: members=%d wgs=%u codes=[%s] MBW=%d\n", h2 ? "f16x2" : "bf16", ks, n, total, codes, mbw);
+  }
   out->fn = kern;
   out->grid = dim3(total);
   out->block = dim3(256);

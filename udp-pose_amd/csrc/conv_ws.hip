@@ -1131,6 +1131,12 @@ int describe_ws_multi(const Launch* members, int n, ConvMulti* m, Launch* out) {
   for (int j = n; j < 5; ++j) m->start[j] = j < 4 ? 0xFFFFFFFFu : total;
   for (int j = n; j < 4; ++j) m->tiles[j] = m->ncby[j] = 1;
   ws_order(m, n);
+  if (getenv("UDP_POSE_DEBUG_TILES")) {
+    char codes[64] = "";
+    for (int j = 0; j < n; ++j) snprintf(codes + strlen(codes), sizeof(codes) - strlen(codes), "%s%d", j ? "," : "", m->code[j]);
+    fprintf(stderr, "ws multi k%d: members=%d wgs=%u codes=[%s] dispatch=%s\n", members[0].groupable / 10 % 10, n, total, codes,
+            m->tab_n ? "table" : "search");
+  }
   out->fn = wk[members[0].groupable / 10 % 10 == 3 ? 0 : 1];
   out->grid = dim3(total);
   out->block = dim3(256);
