@@ -568,6 +568,21 @@ size_t udp_conv2d_wgrad_workspace_bytes(int cout, int cin, int ks);
 int udp_conv2d_wgrad(const void* x, const void* dy, int n, int hin, int win, int cin_k, int hout,
                      int wout, int cout_k, int ks, int stride, int cout, int cin, int dtype, float* dw,
                      int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* Diagnostic, host only (no GPU, no HIP call): the kernel, tile and split-K choice udp_conv2d_wgrad makes for these
+ * arguments and this workspace size -- the launch path calls the same function, so a launch runs exactly what is
+ * reported here.  out[0] = kernel family (0: fp32 MFMA on fp32 tensors, 1: bf16 MFMA on bf16 tensors, 2: bf16 tensors
+ * on the fp32 MFMA kernel, which is what UDP_POSE_WGRAD_F32MFMA selects; the variable is read at every call),
+ * out[1..2] = TW, TH (a unit = TH x TW output pixels of one image), out[3..5] = units per row, per column, in all,
+ * out[6] = upw (units a workgroup walks; the last workgroup may have fewer), out[7] = splits (partials; grid.y),
+ * out[8] = PXP (TH*TW rounded up to 4, family 1: to 16), out[9] = staged rows (PXP + input patch rows),
+ * out[10] = dynamic LDS bytes.  splits = min(target workgroups / channel tiles, units, workspace_bytes / bytes of one
+ * partial), so a caller steers the split count through workspace_bytes.  Returns UDP_OK or the error udp_conv2d_wgrad
+ * would return after its pointer check (shape, output size, workspace smaller than one partial, bf16 pitch, tile
+ * limits).  Channels cin..cin_k of x and cout..cout_k of dy are read but reach no stored element: an MFMA row /
+ * column depends on its own channel only and rows >= cout, columns >= cin are never stored, so the padding need
+ * not be zero.  Adds a symbol only: UDP_POSE_ABI_VERSION stays as it is. */
+int udp_debug_wgrad_tile(int n, int hin, int win, int cin_k, int hout, int wout, int cout_k, int ks, int stride,
+                         int cout, int cin, int dtype, size_t workspace_bytes, int* out);
 /* The weight gradients of up to 4 convs (the same-depth convs of the HRNet branches): the partial-sum kernels run
  * one per member, the fixed-order reduces of all members as ONE launch; results are those of udp_conv2d_wgrad per
  * member, bit for bit.  Every member needs its own workspace. */

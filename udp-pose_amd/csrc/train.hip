@@ -824,10 +824,17 @@ extern "C" size_t udp_conv2d_wgrad_workspace_bytes(int cout, int cin, int ks) {
   return want;
 }
 
-static int wgrad_partials(const void* x, const void* dy, int n, int hin, int win, int cin_k, int hout, int wout,
-                          int cout_k, int ks, int stride, int cout, int cin, int dtype, float* dw,
-                          void* workspace, size_t workspace_bytes, void* stream, int* splits_out) {
-  if (!x || !dy || !dw || !workspace) return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: null pointer");
+// Tile / split choice of the weight gradient, host arithmetic only (no HIP call): wgrad_partials launches exactly what
+// this returns and udp_debug_wgrad_tile reports it.  The refusals are those of udp_conv2d_wgrad after its pointer check.
+struct WgradPlan {
+  int family;                                 // 0 wgrad_kernel<float>, 1 wgrad_bf16_kernel, 2 wgrad_kernel<__bf16>
+  int TH, TW, units_y, units_x, units, upw, splits;
+  int XH, XW, tiles_ci, tiles, pxp;
+  unsigned lds;
+};
+
+static int wgrad_plan(int n, int hin, int win, int cin_k, int hout, int wout, int cout_k, int ks, int stride, int cout,
+                      int cin, int dtype, size_t workspace_bytes, WgradPlan* g) {
   if (check_dtype(dtype, "udp_conv2d_wgrad")) return UDP_ERR_ARG;
   if (n <= 0 || (ks != 1 && ks != 3) || (stride != 1 && stride != 2) || cout <= 0 || cin <= 0 || cout > cout_k ||
       cin > cin_k || (cin_k & 3) || (cout_k & 3))
@@ -835,6 +842,71 @@ static int wgrad_partials(const void* x, const void* dy, int n, int hin, int win
   const int pad = ks / 2;
   if (hout != (hin + 2 * pad - ks) / stride + 1 || wout != (win + 2 * pad - ks) / stride + 1)
     return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: output size does not match input/stride");
+  const bool bf = dtype == UDP_BF16 && getenv("UDP_POSE_WGRAD_F32MFMA") == nullptr;
+  g->family = dtype == UDP_F32 ? 0 : (bf ? 1 : 2);
+  // fp32 kernel: <= 64 pixels per unit; bf16 kernel: up to 256 pixels / 512 staged rows per unit (fewer, larger
+  // global round trips: its MFMA time per unit is far below one HBM latency)
+  const int maxpx = bf ? 256 : (stride == 1 ? 64 : 32);
+  const int nseg = (wout + (bf ? 63 : maxpx - 1)) / (bf ? 64 : maxpx);
+  g->TW = (wout + nseg - 1) / nseg;
+  g->TH = 1;
+  for (int th = maxpx / g->TW; th > 1; --th) {
+    const int rows = ((th * g->TW + 15) & ~15) + ((th - 1) * stride + ks) * ((g->TW - 1) * stride + ks);
+    if (hout % th == 0 && (!bf || rows <= kWbItems * 64)) {
+      g->TH = th;
+      break;
+    }
+  }
+  g->units_x = (wout + g->TW - 1) / g->TW;
+  g->units_y = (hout + g->TH - 1) / g->TH;
+  g->units = n * g->units_x * g->units_y;
+  g->XH = (g->TH - 1) * stride + ks;
+  g->XW = (g->TW - 1) * stride + ks;
+  g->tiles_ci = (cin + 31) / 32;
+  g->tiles = g->tiles_ci * ((cout + 31) / 32);
+  const size_t per = (size_t)ks * ks * cout * cin * sizeof(float);
+  // fp32 kernel: 4 workgroups per CU; bf16 kernel (one resident workgroup per CU, 144 accumulator AGPRs): 1 per CU
+  static const int env_wgs = getenv("UDP_POSE_WGRAD_WGS") ? atoi(getenv("UDP_POSE_WGRAD_WGS")) : 0;
+  const int target_wgs = env_wgs > 0 ? env_wgs : (bf ? 256 : 1024);
+  int splits = (target_wgs + g->tiles - 1) / g->tiles;
+  if (splits > g->units) splits = g->units;
+  if ((size_t)splits * per > workspace_bytes) splits = (int)(workspace_bytes / per);
+  if (splits < 1) return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: workspace of %zu bytes is smaller than one partial (%zu)", workspace_bytes, per);
+  g->upw = (g->units + splits - 1) / splits;
+  g->splits = (g->units + g->upw - 1) / g->upw;
+  g->pxp = bf ? (g->TH * g->TW + 15) & ~15 : (g->TH * g->TW + 3) & ~3;
+  g->lds = (unsigned)((g->pxp + g->XH * g->XW) * kWgPitch * sizeof(float));
+  if (bf) {
+    const int rows = g->pxp + g->XH * g->XW;
+    if (rows * 4 > kWbItems * 256) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_wgrad: tile of %d rows exceeds the staging plan", rows);
+    if ((cin_k & 7) || (cout_k & 7)) return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: bf16 channel pitches must be multiples of 8");
+    g->lds = (unsigned)(rows * kWbPitch);
+    if (g->lds < 4 * 1024 * sizeof(float)) g->lds = 4 * 1024 * sizeof(float);     // the cross-wave reduction buffer
+  }
+  if (g->lds > 160 * 1024) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_wgrad: tile needs %u bytes of LDS", g->lds);
+  return UDP_OK;
+}
+
+extern "C" int udp_debug_wgrad_tile(int n, int hin, int win, int cin_k, int hout, int wout, int cout_k, int ks, int stride,
+                                    int cout, int cin, int dtype, size_t workspace_bytes, int* out) {
+  if (!out) return fail(UDP_ERR_ARG, "udp_debug_wgrad_tile: null pointer");
+  WgradPlan g;
+  memset(&g, 0, sizeof(g));
+  const int rc = wgrad_plan(n, hin, win, cin_k, hout, wout, cout_k, ks, stride, cout, cin, dtype, workspace_bytes, &g);
+  if (rc) return rc;
+  const int v[11] = {g.family, g.TW, g.TH, g.units_x, g.units_y, g.units, g.upw, g.splits, g.pxp, g.pxp + g.XH * g.XW, (int)g.lds};
+  for (int i = 0; i < 11; ++i) out[i] = v[i];
+  return UDP_OK;
+}
+
+static int wgrad_partials(const void* x, const void* dy, int n, int hin, int win, int cin_k, int hout, int wout,
+                          int cout_k, int ks, int stride, int cout, int cin, int dtype, float* dw,
+                          void* workspace, size_t workspace_bytes, void* stream, int* splits_out) {
+  if (!x || !dy || !dw || !workspace) return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: null pointer");
+  WgradPlan g;
+  memset(&g, 0, sizeof(g));
+  const int rc = wgrad_plan(n, hin, win, cin_k, hout, wout, cout_k, ks, stride, cout, cin, dtype, workspace_bytes, &g);
+  if (rc) return rc;
   WgradParams p;
   memset(&p, 0, sizeof(p));
   p.x = x;
@@ -842,60 +914,21 @@ static int wgrad_partials(const void* x, const void* dy, int n, int hin, int win
   p.part = reinterpret_cast<float*>(workspace);
   p.N = n; p.Hin = hin; p.Win = win; p.CinK = cin_k; p.Hout = hout; p.Wout = wout; p.CoutK = cout_k; p.stride = stride;
   p.cout = cout; p.cin = cin;
-  const bool bf = dtype == UDP_BF16 && getenv("UDP_POSE_WGRAD_F32MFMA") == nullptr;
-  // fp32 kernel: <= 64 pixels per unit; bf16 kernel: up to 256 pixels / 512 staged rows per unit (fewer, larger
-  // global round trips: its MFMA time per unit is far below one HBM latency)
-  const int maxpx = bf ? 256 : (stride == 1 ? 64 : 32);
-  const int nseg = (wout + (bf ? 63 : maxpx - 1)) / (bf ? 64 : maxpx);
-  p.TW = (wout + nseg - 1) / nseg;
-  p.TH = 1;
-  for (int th = maxpx / p.TW; th > 1; --th) {
-    const int rows = ((th * p.TW + 15) & ~15) + ((th - 1) * stride + ks) * ((p.TW - 1) * stride + ks);
-    if (hout % th == 0 && (!bf || rows <= kWbItems * 64)) {
-      p.TH = th;
-      break;
-    }
-  }
-  p.units_x = (wout + p.TW - 1) / p.TW;
-  p.units_y = (hout + p.TH - 1) / p.TH;
-  p.units = n * p.units_x * p.units_y;
-  p.XH = (p.TH - 1) * stride + ks;
-  p.XW = (p.TW - 1) * stride + ks;
-  p.tiles_ci = (cin + 31) / 32;
-  const int tiles = p.tiles_ci * ((cout + 31) / 32);
-  const size_t per = (size_t)ks * ks * cout * cin * sizeof(float);
-  // fp32 kernel: 4 workgroups per CU; bf16 kernel (one resident workgroup per CU, 144 accumulator AGPRs): 1 per CU
-  static const int env_wgs = getenv("UDP_POSE_WGRAD_WGS") ? atoi(getenv("UDP_POSE_WGRAD_WGS")) : 0;
-  const int target_wgs = env_wgs > 0 ? env_wgs : (bf ? 256 : 1024);
-  int splits = (target_wgs + tiles - 1) / tiles;
-  if (splits > p.units) splits = p.units;
-  if ((size_t)splits * per > workspace_bytes) splits = (int)(workspace_bytes / per);
-  if (splits < 1) return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: workspace of %zu bytes is smaller than one partial (%zu)", workspace_bytes, per);
-  p.upw = (p.units + splits - 1) / splits;
-  splits = (p.units + p.upw - 1) / p.upw;
-  const int pxp = bf ? (p.TH * p.TW + 15) & ~15 : (p.TH * p.TW + 3) & ~3;
-  unsigned lds = (unsigned)((pxp + p.XH * p.XW) * kWgPitch * sizeof(float));
-  if (bf) {
-    const int rows = pxp + p.XH * p.XW;
-    if (rows * 4 > kWbItems * 256) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_wgrad: tile of %d rows exceeds the staging plan", rows);
-    if ((cin_k & 7) || (cout_k & 7)) return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: bf16 channel pitches must be multiples of 8");
-    lds = (unsigned)(rows * kWbPitch);
-    if (lds < 4 * 1024 * sizeof(float)) lds = 4 * 1024 * sizeof(float);     // the cross-wave reduction buffer
-  }
-  if (lds > 160 * 1024) return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_wgrad: tile needs %u bytes of LDS", lds);
+  p.TH = g.TH; p.TW = g.TW; p.units_y = g.units_y; p.units_x = g.units_x; p.units = g.units; p.upw = g.upw;
+  p.XH = g.XH; p.XW = g.XW; p.tiles_ci = g.tiles_ci;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid(tiles, splits);
+  const dim3 grid(g.tiles, g.splits);
   const void* fn;
-  if (dtype == UDP_F32)
+  if (g.family == 0)
     fn = ks == 3 ? reinterpret_cast<const void*>(&wgrad_kernel<float, 3>) : reinterpret_cast<const void*>(&wgrad_kernel<float, 1>);
-  else if (bf)
+  else if (g.family == 1)
     fn = ks == 3 ? reinterpret_cast<const void*>(&wgrad_bf16_kernel<3>) : reinterpret_cast<const void*>(&wgrad_bf16_kernel<1>);
   else
     fn = ks == 3 ? reinterpret_cast<const void*>(&wgrad_kernel<__bf16, 3>) : reinterpret_cast<const void*>(&wgrad_kernel<__bf16, 1>);
-  if (lds > 64 * 1024) UDP_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (g.lds > 64 * 1024) UDP_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
   void* args[] = {&p};
-  UDP_HIP_CHECK(hipLaunchKernel(fn, grid, dim3(256), args, lds, s));
-  *splits_out = splits;
+  UDP_HIP_CHECK(hipLaunchKernel(fn, grid, dim3(256), args, g.lds, s));
+  *splits_out = g.splits;
   return UDP_OK;
 }
 
