@@ -300,7 +300,36 @@ enum udp_op_kind {
    * honoured (multiples of 8).  `out` must not be `in` or `res`.  relu 0; no second outputs, chain, group, wfmt.  An
    * LDS-tiled VALU kernel (csrc/rsn_gate.hip): the 16 x 24 pixel input tile of an 8 x 16 output tile is staged once.
    * udp_hrnet_flops_per_image counts the 81 MACs per output element. */
-  UDP_OP_PRM_DW9 = 22
+  UDP_OP_PRM_DW9 = 22,
+  /* Activation + squeeze-and-excitation with both biases: what follows `depthwise conv -> BatchNorm` in a MobileNetV3
+   * InvertedResidual (torchvision's mobilenet_v3_small().features -- the backbone of pose_mobilenetv3_small and
+   * pose_mobilenetv3_small_pixel_shuffle, deep_hrnet/lib/models/backbones/mobilenetv3.py:5-16): the block's activation,
+   * then SqueezeExcitation = fc1 (with bias) + ReLU + fc2 (with bias) + Hardsigmoid.  On an NHWC view of C stored
+   * channels, UDP_F32 and UDP_F16X2 (UDP_BF16: UDP_ERR_UNSUPPORTED); one launch, one workgroup per image:
+   *   a[p][c] = act(in[p][c])                 act = `relu`: UDP_ACT_NONE | UDP_ACT_RELU | UDP_ACT_HSWISH
+   *   mean[c] = (1 / HW) sum_p a[p][c]        h = relu(W1 mean + b1)                 (Ch = chain_cout rows)
+   *   m[c] = clamp((W2 h)[c] + b2[c] + 3, 0, 6) / 6                                  (torch Hardsigmoid)
+   *   out[p][c] = a[p][c] * m[c]
+   * The activation is applied while the map is pooled and again while it is scaled, so the map is read twice and
+   * written once -- where UDP_OP_DWCONV (no hard-swish epilogue) + UDP_OP_ACT + UDP_OP_SE would read and write it
+   * twice and still lack b2.  cin == cout == cout_pad = C, a multiple of 32, 32 <= C <= 1024; chain_cout = Ch,
+   * 1 <= Ch <= min(256, C) -- a count, as for kind 14, no chained conv; hout == hin, wout == win, any size >= 1.
+   * Activation code 4 (SiLU): UDP_ERR_UNSUPPORTED; code 3 and codes outside 0..4: UDP_ERR_ARG.  in_coff / in_pitch /
+   * out_coff / out_pitch are honoured (multiples of 8).  `out` MAY be `in` (same buffer, same view -- the rule of kind
+   * 14): the pool is complete before the first store and every element is read and written by one thread; any other
+   * overlap of the two is refused.  No res, addends, second outputs, group, wfmt.  Parameter block at w_off
+   * (udp_conv2d_fused: `weights`; `bias` may be NULL), fp32 in EVERY storage mode: W1 transposed [C][Ch], b1 [Ch], W2
+   * transposed [Ch][C], b2 [C]; udp_hrnet_create checks its (2 C Ch + Ch + C) * 4 bytes against the blob.  Pad
+   * channels carry zero weights and zero b2: m = 0.5 there, and act(0) * 0.5 = 0 keeps them exact zeros.  All
+   * arithmetic is fp32, hard-swish exactly the formula at UDP_ACT_HSWISH below; UDP_F16X2 inputs are decoded hi + lo *
+   * 2^-11 and the result is split again on store, with the udp_f16x2_overflow range guard.  Sums as kind 14: the pool
+   * by P = max(1, 256 / (C / V)) pixel groups per channel (V = 4 fp32 / 8 split-fp16 channels per thread) added in
+   * group order, W1 mean by Q channel parts (fmaf from 0 in channel order) added in part order onto b1, W2 h by fmaf
+   * from 0 in the order j = 0 .. Ch-1, then + b2 + 3; P, Q depend on (C, Ch) only, nothing is atomic: an image's
+   * result does not depend on the batch it arrives in, on the lane or on graph replay.  The dynamic LDS is sized from
+   * C.  It adds a kind and no field or symbol: UDP_POSE_ABI_VERSION stays as it is.  udp_hrnet_flops_per_image counts
+   * 4 C Ch (the two small products), as for kind 14. */
+  UDP_OP_SE_ACT = UDP_OP_PRM_DW9 + 1 /* kind 23 */
 };
 
 /* udp_conv_op.relu is an activation code.  UDP_ACT_HSWISH: v * (clamp(v + 3, 0, 6) / 6) in fp32, applied where the
@@ -310,7 +339,8 @@ enum udp_op_kind {
  * UDP_ACT_SILU ("swish", nn.SiLU: the activation of every ConvLayer of MobileViTv2, backbones/mobilevitv2.py:78-79):
  * v * (1 / (1 + expf(-v))) in fp32, in the same place -- honoured by the two forms above and by UDP_OP_DWCONV (every
  * ks / stride it has); every other op and conv form answers it with UDP_ERR_UNSUPPORTED.  silu(0) = 0, so zero pad
- * channels stay exact zeros.  Code 3 is not assigned and stays refused with UDP_ERR_ARG, as every code outside 0..4. */
+ * channels stay exact zeros.  Code 3 is not assigned and stays refused with UDP_ERR_ARG, as every code outside 0..4.
+ * UDP_OP_SE_ACT reads the field as the activation of its INPUT (codes 0, 1 and 2; kind 23 above). */
 #define UDP_ACT_NONE 0
 #define UDP_ACT_RELU 1
 #define UDP_ACT_HSWISH 2
@@ -416,8 +446,8 @@ double udp_hrnet_flops_per_image(const udp_hrnet* h);
 
 /* One fused conv launch on raw pointers (the operator the program above is made of; used by
  * the per-layer parity tests and kernel benchmarks).  `op` supplies kind (UDP_OP_CONV, UDP_OP_FUSE,
- * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM, UDP_OP_LINATTN, UDP_OP_LNORM, UDP_OP_MHATTN, UDP_OP_ACT, UDP_OP_SE_RES, UDP_OP_PRM_GATE or UDP_OP_PRM_DW9: NHWC in / out, weights as documented there, no res / up -- except the
- * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`; UDP_OP_SE / UDP_OP_GNORM: `weights` = the parameter block, chain_cout = hidden width / real channels;
+ * UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM, UDP_OP_LINATTN, UDP_OP_LNORM, UDP_OP_MHATTN, UDP_OP_ACT, UDP_OP_SE_RES, UDP_OP_PRM_GATE, UDP_OP_PRM_DW9 or UDP_OP_SE_ACT: NHWC in / out, weights as documented there, no res / up -- except the
+ * passthrough of UDP_OP_DWCONV: source `res`, destination `up0`; UDP_OP_SE / UDP_OP_SE_ACT / UDP_OP_GNORM: `weights` = the parameter block, chain_cout = hidden width / real channels;
  * UDP_OP_LNORM: `weights` = the parameter block, chain_cout = real channels; UDP_OP_MHATTN: no weights, chain_cout = real width, up_shift[0] = heads;
  * UDP_OP_LINATTN / UDP_OP_ACT: no weights; UDP_OP_SE_RES: `weights` = the parameter block, chain_cout = hidden width, `res` = the shortcut or NULL;
  * UDP_OP_PRM_GATE: `weights` = the parameter block, `out` = fp32 [n][C]; UDP_OP_PRM_DW9: `res` = out_1, `up0` = the fp32 rows of UDP_OP_PRM_GATE), ks, stride, relu, cin, cout, cout_pad, hin, win, hout, wout, n_up, up_shift;

@@ -4,7 +4,8 @@ per-op-class kernel time of udp_hrnet_profile (hipEvents around every launch, ea
 the achieved bytes/s on its algorithmic traffic (one read and one write of the map) next to the launch time of a
 UDP_OP_FUSE (an existing kernel that moves the same bytes) on a tensor of the same size, in the same session.
 
-    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32] [--model v2|plus|mobilevitv2|mobilevit]
+    python tools/bench_shufflenet.py [--steps 20] [--warmup 5] [--batch 64] [--dtypes f16x2,f32] [--model v2|plus|mobilevitv2|mobilevit|
+                                         mobilenetv3|mobilenetv3_deconv|v2_deconv|plus_deconv]
 
 ``--model plus``: pose_shufflenetv2_plus_pixel_shuffle (Small) instead, with the same measurements; its depthwise
 launches are classed by kernel size, and the squeeze-excitation launches and the 1x1 convs with the hard-swish
@@ -18,6 +19,10 @@ UDP_OP_FUSE launch on the map they read.
 ``--model mobilevit``: pose_mobilevit_pixel_shuffle (MODEL_SIZE xxs) instead; layer norm, multi-head attention, the
 stand-alone activation launches, the 1x1 convs by epilogue and the 3x3 convs get classes of their own (no side
 measurement).
+
+``--model mobilenetv3 | mobilenetv3_deconv | v2_deconv | plus_deconv``: pose_mobilenetv3_small_pixel_shuffle,
+pose_mobilenetv3_small, pose_shufflenetv2_10x (1.0x) and pose_shufflenetv2_plus (Small) instead, with the classes of
+``--model plus`` plus ``se_act`` (UDP_OP_SE_ACT), ``deconv`` and ``conv1x1_res`` (the project convs with their shortcut).
 """
 import argparse
 import ctypes as C
@@ -46,6 +51,27 @@ MVIT_NAME = "pose_mobilevitv2_pixel_shuffle"
 MVIT_EXTRA = dict(EXTRA, MODEL_SIZE=0.5)
 VIT_NAME = "pose_mobilevit_pixel_shuffle"
 VIT_EXTRA = dict(EXTRA, MODEL_SIZE="xxs")
+DECONV = {"DECONV_WITH_BIAS": False, "NUM_DECONV_LAYERS": 3, "NUM_DECONV_FILTERS": [256, 256, 256], "NUM_DECONV_KERNELS": [4, 4, 4],
+          "FINAL_CONV_KERNEL": 1}
+
+
+def _later_nets():
+    """--model choice -> (MODEL.NAME, MODEL.EXTRA, seeded state dict, workload text) of the MobileNetV3 nets and the
+    deconv-head ShuffleNets."""
+    from udp_pose_amd.synth_mobilenetv3 import synth_mobilenetv3_state_dict
+    from udp_pose_amd.synth_shufflenet import synth_shufflenet_deconv_state_dict
+    from udp_pose_amd.synth_shufflenet_plus import synth_shufflenet_plus_deconv_state_dict
+    return {"mobilenetv3": ("pose_mobilenetv3_small_pixel_shuffle", dict(EXTRA, MODEL_SIZE="small"),
+                            lambda: synth_mobilenetv3_state_dict(seed=7), "pose_mobilenetv3_small_pixel_shuffle"),
+            "mobilenetv3_deconv": ("pose_mobilenetv3_small", dict(DECONV, MODEL_SIZE="small"),
+                                   lambda: synth_mobilenetv3_state_dict(seed=7, head="deconv"), "pose_mobilenetv3_small"),
+            "v2_deconv": ("pose_shufflenetv2_10x", dict(DECONV, MODEL_SIZE="1.0x"), lambda: synth_shufflenet_deconv_state_dict(seed=7),
+                          "pose_shufflenetv2_10x 1.0x"),
+            "plus_deconv": ("pose_shufflenetv2_plus", dict(DECONV, MODEL_SIZE="Small"), lambda: synth_shufflenet_plus_deconv_state_dict(seed=7),
+                            "pose_shufflenetv2_plus Small")}
+
+
+LATER = ("mobilenetv3", "mobilenetv3_deconv", "v2_deconv", "plus_deconv")
 
 
 def op_class(name, kind, ks, stride):
@@ -69,6 +95,12 @@ def op_class_plus(op):
         return "dwconv%d_s%d" % (op["ks"], op["stride"])
     if op["kind"] == _lib.UDP_OP_SE:
         return "se"
+    if op["kind"] == _lib.UDP_OP_SE_ACT:
+        return "se_act"
+    if op["kind"] == _lib.UDP_OP_DECONV:
+        return "deconv"
+    if op["kind"] == _lib.UDP_OP_CONV and op["ks"] == 1 and op["res"] is not None:
+        return "conv1x1_res"
     if op["kind"] == _lib.UDP_OP_CONV and op["relu"] == _lib.UDP_ACT_HSWISH:
         return "conv1x1_hs"
     return op_class(op["name"], op["kind"], op["ks"], op["stride"])
@@ -174,11 +206,16 @@ def attn_vs_fuse(dtype, images, c=64, h=32, w=24):
             "us_min_max": [[round(lo * 1e3, 2), round(hi * 1e3, 2)] for _, lo, hi in t]}
 
 
-def run(dtype, n, steps, warmup, plus=False, mvit=False, vit=False):
+def run(dtype, n, steps, warmup, plus=False, mvit=False, vit=False, later=None):
     name = VIT_NAME if vit else MVIT_NAME if mvit else PLUS_NAME if plus else NAME
     cfg = {"MODEL": {"NAME": name, "NUM_JOINTS": 17, "TARGET_TYPE": "gaussian",
                      "EXTRA": VIT_EXTRA if vit else MVIT_EXTRA if mvit else PLUS_EXTRA if plus else EXTRA}}
-    if vit:
+    if later:
+        name, extra, make_sd, _ = _later_nets()[later]
+        cfg["MODEL"].update(NAME=name, EXTRA=extra)
+        sd = make_sd()
+        plus = True                  # the classes of op_class_plus (with se_act, deconv and the residual 1x1 convs)
+    elif vit:
         from udp_pose_amd.synth_mobilevit import synth_mobilevit_state_dict
         sd = synth_mobilevit_state_dict(seed=7)
     elif mvit:
@@ -228,11 +265,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--dtypes", default="f16x2,f32")
-    ap.add_argument("--model", choices=("v2", "plus", "mobilevitv2", "mobilevit"), default="v2")
+    ap.add_argument("--model", choices=("v2", "plus", "mobilevitv2", "mobilevit") + LATER, default="v2")
     a = ap.parse_args()
     plus, mvit, vit = a.model == "plus", a.model == "mobilevitv2", a.model == "mobilevit"
-    res = [run(d, a.batch, a.steps, a.warmup, plus, mvit, vit) for d in a.dtypes.split(",")]
-    workload = ("pose_mobilevit_pixel_shuffle xxs" if vit else "pose_mobilevitv2_pixel_shuffle 0.5" if mvit else "pose_shufflenetv2_plus_pixel_shuffle Small" if plus
+    later = a.model if a.model in LATER else None
+    res = [run(d, a.batch, a.steps, a.warmup, plus, mvit, vit, later) for d in a.dtypes.split(",")]
+    workload = (_later_nets()[later][3] if later else "pose_mobilevit_pixel_shuffle xxs" if vit else "pose_mobilevitv2_pixel_shuffle 0.5" if mvit else "pose_shufflenetv2_plus_pixel_shuffle Small" if plus
                 else "pose_shufflenetv2_10x_pixel_shuffle 1.0x")
     out = {"workload": workload + " 256x192 flip-test + DARK decode", "batch": a.batch, "results": res}
     if len(res) == 2:

@@ -18,6 +18,7 @@ UDP_OP_PSA_POOL, UDP_OP_PSA_MLP, UDP_OP_PSA_SCALE, UDP_OP_PSA_SP, UDP_OP_BLOCK =
 UDP_OP_DECONV, UDP_OP_DWCONV, UDP_OP_PIXSHUF, UDP_OP_SE, UDP_OP_GNORM, UDP_OP_LINATTN = 11, 12, 13, 14, 15, 16
 UDP_OP_LNORM, UDP_OP_MHATTN, UDP_OP_ACT = 17, 18, 19
 UDP_OP_SE_RES, UDP_OP_PRM_GATE, UDP_OP_PRM_DW9 = 20, 21, 22       # the gates of RSN-18 "se + prm" (csrc/rsn_gate.hip)
+UDP_OP_SE_ACT = 23       # activation + squeeze-and-excitation with both biases: MobileNetV3 (csrc/dwconv.hip)
 UDP_ACT_NONE, UDP_ACT_RELU, UDP_ACT_HSWISH, UDP_ACT_SILU = 0, 1, 2, 4      # udp_conv_op.relu is an activation code (3: not assigned)
 UDP_BUF_NONE, UDP_BUF_OUTPUT = -1, -2
 ABI_VERSION = 19

@@ -184,6 +184,8 @@ int describe_dwconv(ConvParams p, int dtype, int ks, int stride, Launch* out);
 int describe_pixshuf(ConvParams p, int dtype, Launch* out);
 int se_validate(const udp_conv_op& o, int dtype);                // UDP_OP_SE (squeeze-and-excitation, one workgroup per image)
 int describe_se(ConvParams p, int dtype, Launch* out);
+int se_act_validate(const udp_conv_op& o, int dtype);            // UDP_OP_SE_ACT (activation + squeeze-and-excitation with both biases, C up to 1024)
+int describe_se_act(ConvParams p, int dtype, Launch* out);
 int dwconv_h2_overflow(hipStream_t s, int reset, int* flag);
 // attn.hip: GroupNorm(1, C) (UDP_OP_GNORM) and the separable self-attention core (UDP_OP_LINATTN), one workgroup per image
 int gnorm_validate(const udp_conv_op& o, int dtype);

@@ -300,6 +300,105 @@ __global__ __launch_bounds__(256) void se_kernel(const ConvParams p) {
   }
 }
 
+// Activation + squeeze-and-excitation with both biases (UDP_OP_SE_ACT; torchvision's SqueezeExcitation behind the
+// depthwise conv + BatchNorm + activation of a MobileNetV3 InvertedResidual) on an NHWC view of C = p.Cin stored
+// channels, C up to 1024: se_kernel's four phases with a[p][c] = act(in[p][c]) in place of in[p][c] in the pool and
+// in the scale, b2 added in phase 3, and the pool's partial sums sized from C --
+//   1. P = max(1, 256 / (C / V)) pixel groups (at most HW): thread (g, channel group) adds act(in) of pixels g, g + P,
+//      ... in that order; the P partial sums of a channel are added in the order g = 0 .. P-1, times 1 / HW.  Beyond
+//      128 channel groups (C = 576 in fp32: 144) P is 1: a thread walks every pixel and the other threads sit idle;
+//   2. h[j] = relu(b1[j] + sum_c W1[c][j] mean[c]) exactly as se_kernel (Q channel parts, added in part order);
+//   3. m[c] = clamp((sum_j W2[j][c] h[j]) + b2[c] + 3, 0, 6) / 6, fmaf from 0 in the order j = 0 .. Ch-1;
+//   4. out = act(in) * m[c], every element by one thread (so `out` may be the very view `in` is).
+// ACT = udp_conv_op.relu: UDP_ACT_NONE | UDP_ACT_RELU | UDP_ACT_HSWISH (describe_se_act clears p.relu: dw_store must not
+// put a ReLU behind the product -- hswish(v) * m is negative for -3 < v < 0).  Parameter block (fp32): W1 [C][Ch],
+// b1 [Ch], W2 [Ch][C], b2 [C].  Dynamic LDS: (P * C + 2 * C + 256 + Ch) floats, P before the clamp to HW.
+static_assert(UDP_OP_SE_ACT == 23, "udp_pose_hip.h: UDP_OP_SE_ACT follows UDP_OP_PRM_DW9 (_lib.py binds 23)");
+
+template <int ACT>
+__device__ __forceinline__ float se_act_in(float v) {
+  if constexpr (ACT == UDP_ACT_RELU) return __builtin_fmaxf(v, 0.f);
+  else if constexpr (ACT == UDP_ACT_HSWISH) return hswish(v);
+  else return v;
+}
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void se_act_kernel(const ConvParams p) {
+  constexpr int V = DwTr<T>::V;
+  extern __shared__ __attribute__((aligned(16))) float se_s[];
+  const int C = p.Cin, Ch = p.up_shift[0], HW = p.Hin * p.Win;
+  const int cgs = C / V;                                    // <= 256 (se_act_validate: C <= 1024)
+  const int P0 = 256 / cgs > 1 ? 256 / cgs : 1;
+  float* part = se_s;                  // [P0][C]
+  float* mean = part + (size_t)P0 * C; // [C]
+  float* mul = mean + C;               // [C]
+  float* hpart = mul + C;              // [Q][Ch], Q * Ch <= 256
+  float* hid = hpart + 256;            // [Ch]
+  const int tid = threadIdx.x;
+  const size_t img = (size_t)blockIdx.x * HW;
+  const int P = P0 < HW ? P0 : HW;
+  {
+    const int cg = tid % cgs, g = tid / cgs;
+    if (g < P) {
+      float s[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) s[k] = 0.f;
+      for (int px = g; px < HW; px += P) {
+        float x[V];
+        dw_load<T, V>(p, img + px, cg * V, x);
+#pragma unroll
+        for (int k = 0; k < V; ++k) s[k] += se_act_in<ACT>(x[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < V; ++k) part[g * C + cg * V + k] = s[k];
+    }
+  }
+  __syncthreads();
+  const float inv = 1.f / (float)HW;
+  for (int c = tid; c < C; c += 256) {
+    float s = part[c];
+    for (int g = 1; g < P; ++g) s += part[g * C + c];
+    mean[c] = s * inv;
+  }
+  __syncthreads();
+  const float* w1 = reinterpret_cast<const float*>(p.wgt);
+  const float* b1 = w1 + (size_t)C * Ch;
+  const float* w2 = b1 + Ch;
+  const float* b2 = w2 + (size_t)Ch * C;
+  const int Q = 256 / Ch < C ? 256 / Ch : C;            // Ch <= 256
+  const int L = (C + Q - 1) / Q;
+  {
+    const int j = tid % Ch, q = tid / Ch;
+    if (q < Q) {
+      const int c0 = q * L < C ? q * L : C, c1 = (q + 1) * L < C ? (q + 1) * L : C;
+      float s = 0.f;
+      for (int c = c0; c < c1; ++c) s = __builtin_fmaf(w1[(size_t)c * Ch + j], mean[c], s);
+      hpart[q * Ch + j] = s;
+    }
+  }
+  __syncthreads();
+  if (tid < Ch) {
+    float s = b1[tid];
+    for (int q = 0; q < Q; ++q) s += hpart[q * Ch + tid];
+    hid[tid] = __builtin_fmaxf(s, 0.f);
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float s = 0.f;
+    for (int j = 0; j < Ch; ++j) s = __builtin_fmaf(w2[(size_t)j * C + c], hid[j], s);
+    mul[c] = __builtin_fminf(__builtin_fmaxf(s + b2[c] + 3.f, 0.f), 6.f) / 6.f;
+  }
+  __syncthreads();
+  for (int e = tid; e < HW * cgs; e += 256) {
+    const int cg = e % cgs, px = e / cgs;
+    float x[V];
+    dw_load<T, V>(p, img + px, cg * V, x);
+#pragma unroll
+    for (int k = 0; k < V; ++k) x[k] = se_act_in<ACT>(x[k]) * mul[cg * V + k];
+    dw_store<T, V>(p, img + px, cg * V, x);
+  }
+}
+
 // PixelShuffle(2) on NHWC with the four sub-pixel groups contiguous per pixel: group g = 2i + j (cout channels from
 // g * cout) of input pixel (h, w) -> output pixel (2h + i, 2w + j).  thread = (image, h, w, g, channel group).
 template <typename T>
@@ -375,6 +474,26 @@ int se_validate(const udp_conv_op& o, int dtype) {
   return UDP_OK;
 }
 
+// UDP_OP_SE_ACT: cin == cout stored channels (a multiple of 32, 32 .. 1024), chain_cout = hidden width (1 .. min(256, C)),
+// relu = the activation applied to the input: 0 | 1 | 2 (hrnet.hip's act_validate has refused code 3 and codes outside 0..4)
+int se_act_validate(const udp_conv_op& o, int dtype) {
+  if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "activation + squeeze-excitation: storage modes f32 and f16x2 only");
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "activation + squeeze-excitation: dtype %d", dtype);
+  if (o.relu < 0 || o.relu > UDP_ACT_SILU || o.relu == 3) return fail(UDP_ERR_ARG, "activation + squeeze-excitation: activation code %d", o.relu);
+  if (o.relu == UDP_ACT_SILU) return fail(UDP_ERR_UNSUPPORTED, "activation + squeeze-excitation: no SiLU form (activation code 4)");
+  if (o.cin < 32 || o.cin != o.cout || o.cin % 32 || o.cin > 1024 || o.cout_pad != o.cout || o.chain_cout < 1 || o.chain_cout > 256 ||
+      o.chain_cout > o.cin || o.hin < 1 || o.win < 1 || o.hout != o.hin || o.wout != o.win ||
+      (int64_t)o.hin * o.win * (o.cin / 4) >= (1LL << 31))
+    return fail(UDP_ERR_ARG, "activation + squeeze-excitation: cin == cout == cout_pad, a multiple of 32 from 32 to 1024, hidden width "
+                "(chain_cout) 1 .. min(256, cin), output = input size (C%d->%d, hidden %d)", o.cin, o.cout, o.chain_cout);
+  const int ipitch = o.in_pitch ? o.in_pitch : o.cin, opitch = o.out_pitch ? o.out_pitch : o.cout;
+  if (o.in_coff < 0 || o.out_coff < 0 || o.in_coff + o.cin > ipitch || o.out_coff + o.cout > opitch || (o.in_coff | ipitch | o.out_coff | opitch) % 8)
+    return fail(UDP_ERR_ARG, "activation + squeeze-excitation: channel views");
+  if (o.n_up || o.n_out2 || o.group || o.in_stuff2 || o.wfmt || o.out_buf == UDP_BUF_OUTPUT)
+    return fail(UDP_ERR_UNSUPPORTED, "activation + squeeze-excitation: no addends, second outputs, groups, wfmt or NCHW output");
+  return UDP_OK;
+}
+
 int pixshuf_validate(const udp_conv_op& o, int dtype) {
   if (dtype == UDP_BF16) return fail(UDP_ERR_UNSUPPORTED, "pixel shuffle: storage modes f32 and f16x2 only");
   if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_ARG, "pixel shuffle: dtype %d", dtype);
@@ -442,6 +561,29 @@ int describe_se(ConvParams p, int dtype, Launch* out) {
   out->grid = dim3((unsigned)p.N);
   out->block = dim3(256);
   out->lds = (unsigned)((256 * V + 2 * p.Cin + 256 + Ch) * sizeof(float));
+  out->p = p;
+  return UDP_OK;
+}
+
+// p: geometry, views, in / out, wgt = the parameter block, up_shift[0] = hidden width, relu = the activation applied to
+// the INPUT (it picks the instantiation; the store applies none).  One workgroup per image, LDS sized from C.
+int describe_se_act(ConvParams p, int dtype, Launch* out) {
+  if (dtype != UDP_F32 && dtype != UDP_F16X2) return fail(UDP_ERR_UNSUPPORTED, "activation + squeeze-excitation: storage modes f32 and f16x2 only");
+  if (!p.in || !p.out || !p.wgt) return fail(UDP_ERR_ARG, "activation + squeeze-excitation: null pointer");
+  const int V = dtype == UDP_F32 ? 4 : 8, Ch = p.up_shift[0], act = p.relu;
+  if (p.Cin < 32 || p.Cin % 32 || p.Cin > 1024 || Ch < 1 || Ch > 256 || Ch > p.Cin || p.N <= 0 || p.Hin < 1 || p.Win < 1)
+    return fail(UDP_ERR_ARG, "activation + squeeze-excitation: C %d, hidden %d", p.Cin, Ch);
+  if (act != UDP_ACT_NONE && act != UDP_ACT_RELU && act != UDP_ACT_HSWISH) return fail(UDP_ERR_ARG, "activation + squeeze-excitation: activation code %d", act);
+#define UDP_SEA(T) (act == UDP_ACT_HSWISH ? reinterpret_cast<const void*>(&se_act_kernel<T, UDP_ACT_HSWISH>) \
+                    : act == UDP_ACT_RELU ? reinterpret_cast<const void*>(&se_act_kernel<T, UDP_ACT_RELU>)   \
+                                          : reinterpret_cast<const void*>(&se_act_kernel<T, UDP_ACT_NONE>))
+  out->fn = dtype == UDP_F32 ? UDP_SEA(float) : UDP_SEA(H2);
+#undef UDP_SEA
+  const int cgs = p.Cin / V, P0 = 256 / cgs > 1 ? 256 / cgs : 1;
+  p.relu = 0;
+  out->grid = dim3((unsigned)p.N);
+  out->block = dim3(256);
+  out->lds = (unsigned)(((size_t)P0 * p.Cin + 2 * p.Cin + 256 + Ch) * sizeof(float));
   out->p = p;
   return UDP_OK;
 }

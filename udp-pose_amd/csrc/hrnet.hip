@@ -66,7 +66,7 @@ static size_t esize(int dtype) { return dtype == UDP_BF16 ? 2 : 4; }   // bytes 
 static int act_validate(const udp_conv_op& o, int dtype, bool has_res) {
   if (o.relu < UDP_ACT_NONE || o.relu > UDP_ACT_SILU || o.relu == 3)
     return fail(UDP_ERR_ARG, "activation code %d (0 none, 1 ReLU, 2 hard-swish, 4 SiLU)", o.relu);
-  if (o.relu < UDP_ACT_HSWISH || o.kind == UDP_OP_ACT) return UDP_OK;      // (UDP_OP_ACT: act_op_validate has its rules)
+  if (o.relu < UDP_ACT_HSWISH || o.kind == UDP_OP_ACT || o.kind == UDP_OP_SE_ACT) return UDP_OK;      // (act_op_validate / se_act_validate have their rules)
   if (o.relu == UDP_ACT_SILU && o.kind == UDP_OP_DWCONV) return UDP_OK;      // (dwconv_validate refuses bf16)
   const bool plain1x1 = o.kind == UDP_OP_CONV && o.ks == 1 && o.stride == 1 && !o.group && !o.chain_cout && !o.n_up && !o.n_out2 && !has_res &&
                         !o.in_stuff2 && o.out_buf != UDP_BUF_OUTPUT;
@@ -81,7 +81,7 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
   const int nb = (int)h->buf_elems.size();
   auto buf_ok = [&](int b, int64_t need) { return b >= 0 && b < nb && h->buf_elems[b] >= need; };
   const int64_t out_need = (int64_t)o.hout * o.wout * (o.out_pitch ? o.out_pitch : o.cout);
-  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_PRM_DW9) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
+  if (o.kind < UDP_OP_STEM || o.kind > UDP_OP_SE_ACT) return fail(UDP_ERR_ARG, "op %d: bad kind %d", idx, o.kind);
   if (const int rc = act_validate(o, h->dtype, o.res_buf != UDP_BUF_NONE)) return rc;
   if (o.lane < 0 || o.lane >= UDP_MAX_LANES || o.n_wait < 0 || o.n_wait > UDP_MAX_WAIT) return fail(UDP_ERR_ARG, "op %d: lane/n_wait", idx);
   for (int k = 0; k < o.n_wait; ++k)
@@ -132,6 +132,20 @@ static int validate_op(const udp_hrnet* h, const udp_conv_op& o, int idx) {
     const size_t wbytes = ((size_t)2 * o.cin * o.chain_cout + o.chain_cout) * 4;
     if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15))
       return fail(UDP_ERR_ARG, "op %d: squeeze-excitation parameter block outside the blob or misaligned", idx);
+    return UDP_OK;
+  }
+  if (o.kind == UDP_OP_SE_ACT) {
+    // activation + squeeze-and-excitation with both biases (dwconv.hip); `out` may be the very view `in` is
+    const int rc = se_act_validate(o, h->dtype);
+    if (rc) return rc;
+    const int ipitch = o.in_pitch ? o.in_pitch : o.cin;
+    if (!buf_ok(o.in_buf, (int64_t)o.hin * o.win * ipitch) || !buf_ok(o.out_buf, out_need) || o.res_buf != UDP_BUF_NONE)
+      return fail(UDP_ERR_ARG, "op %d: activation + squeeze-excitation buffers missing or too small (or a residual)", idx);
+    if (o.in_buf == o.out_buf && (o.in_coff != o.out_coff || ipitch != (o.out_pitch ? o.out_pitch : o.cout)))
+      return fail(UDP_ERR_ARG, "op %d: activation + squeeze-excitation in place needs the same view for in and out", idx);
+    const size_t wbytes = ((size_t)2 * o.cin * o.chain_cout + o.chain_cout + o.cin) * 4;      // W1, b1, W2, b2
+    if (o.w_off < 0 || (size_t)o.w_off + wbytes > h->weights_bytes || (o.w_off & 15))
+      return fail(UDP_ERR_ARG, "op %d: activation + squeeze-excitation parameter block outside the blob or misaligned", idx);
     return UDP_OK;
   }
   if (o.kind == UDP_OP_SE_RES || o.kind == UDP_OP_PRM_GATE || o.kind == UDP_OP_PRM_DW9) {
@@ -382,6 +396,7 @@ extern "C" int udp_hrnet_create(const udp_conv_op* ops, int n_ops, const int64_t
     if (ops[i].kind == UDP_OP_DWCONV) h->flops += 2.0 * ops[i].ks * ops[i].ks * ops[i].cout * ops[i].hout * ops[i].wout;   // ks * ks MACs per output element
     if (ops[i].kind == UDP_OP_SE) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // the two small products (pool and scale are not counted)
     if (ops[i].kind == UDP_OP_SE_RES) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // as UDP_OP_SE
+    if (ops[i].kind == UDP_OP_SE_ACT) h->flops += 2.0 * 2 * ops[i].cin * ops[i].chain_cout;   // as UDP_OP_SE (activation, biases, pool and scale are not counted)
     if (ops[i].kind == UDP_OP_PRM_GATE) h->flops += 2.0 * 2 * ops[i].cin * ops[i].cin;
     if (ops[i].kind == UDP_OP_PRM_DW9) h->flops += 2.0 * 81 * ops[i].cout * ops[i].hout * ops[i].wout;   // the taps (the gate's epilogue is not counted)
     if (ops[i].kind == UDP_OP_LINATTN) h->flops += 2.0 * ops[i].cout * ops[i].hout * ops[i].wout;   // the weighted sum of the keys (soft-max and gate are not counted)
@@ -712,7 +727,7 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, in
       p.up_shift[2] = o.chain_relu;
     }
     if (o.kind == UDP_OP_DWCONV) p.up_shift[0] = o.chain_cout;   // passthrough: real channels per half (n_up == 0)
-    if (o.kind == UDP_OP_SE || o.kind == UDP_OP_GNORM || o.kind == UDP_OP_LNORM) {
+    if (o.kind == UDP_OP_SE || o.kind == UDP_OP_GNORM || o.kind == UDP_OP_LNORM || o.kind == UDP_OP_SE_ACT) {
       p.wgt = h->weights + o.w_off;
       p.up_shift[0] = o.chain_cout;                              // hidden width / real channels
     }
@@ -748,6 +763,7 @@ static int describe_all(const udp_hrnet* h, const float* in, int n, int flip, in
       case UDP_OP_DECONV: rc = describe_deconv(p, h->dtype, &ls[i]); break;
       case UDP_OP_DWCONV: rc = describe_dwconv(p, h->dtype, o.ks, o.stride, &ls[i]); break;
       case UDP_OP_SE: rc = describe_se(p, h->dtype, &ls[i]); break;
+      case UDP_OP_SE_ACT: rc = describe_se_act(p, h->dtype, &ls[i]); break;
       case UDP_OP_GNORM: rc = describe_gnorm(p, h->dtype, &ls[i]); break;
       case UDP_OP_LINATTN: rc = describe_linattn(p, h->dtype, &ls[i]); break;
       case UDP_OP_LNORM: rc = describe_lnorm(p, h->dtype, &ls[i]); break;
@@ -1144,16 +1160,23 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   if (n <= 0) return fail(UDP_ERR_ARG, "udp_conv2d_fused: n=%d", n);
   if (o->kind != UDP_OP_CONV && o->kind != UDP_OP_FUSE && o->kind != UDP_OP_DECONV && o->kind != UDP_OP_DWCONV && o->kind != UDP_OP_PIXSHUF &&
       o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_LNORM && o->kind != UDP_OP_MHATTN &&
-      o->kind != UDP_OP_ACT && o->kind != UDP_OP_SE_RES && o->kind != UDP_OP_PRM_GATE && o->kind != UDP_OP_PRM_DW9)
+      o->kind != UDP_OP_ACT && o->kind != UDP_OP_SE_RES && o->kind != UDP_OP_PRM_GATE && o->kind != UDP_OP_PRM_DW9 && o->kind != UDP_OP_SE_ACT)
     return fail(UDP_ERR_ARG, "udp_conv2d_fused: kind %d", o->kind);
   if (const int rc = act_validate(*o, dtype, res != nullptr)) return rc;
-  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_MHATTN && o->kind != UDP_OP_ACT && (!weights || (!bias && o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LNORM && o->kind != UDP_OP_SE_RES && o->kind != UDP_OP_PRM_GATE))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
+  if (o->kind != UDP_OP_FUSE && o->kind != UDP_OP_PIXSHUF && o->kind != UDP_OP_LINATTN && o->kind != UDP_OP_MHATTN && o->kind != UDP_OP_ACT && (!weights || (!bias && o->kind != UDP_OP_SE && o->kind != UDP_OP_GNORM && o->kind != UDP_OP_LNORM && o->kind != UDP_OP_SE_RES && o->kind != UDP_OP_PRM_GATE && o->kind != UDP_OP_SE_ACT))) return fail(UDP_ERR_ARG, "udp_conv2d_fused: conv needs weights and bias");
   if (o->kind == UDP_OP_SE) {
     const int rc = se_validate(*o, dtype);
     if (rc) return rc;
     if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation takes no residual");
     if (in == out && (o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
       return fail(UDP_ERR_ARG, "udp_conv2d_fused: squeeze-excitation in place needs the same view for in and out");
+  }
+  if (o->kind == UDP_OP_SE_ACT) {
+    const int rc = se_act_validate(*o, dtype);
+    if (rc) return rc;
+    if (res) return fail(UDP_ERR_ARG, "udp_conv2d_fused: activation + squeeze-excitation takes no residual");
+    if (in == out && (o->in_coff != o->out_coff || (o->in_pitch ? o->in_pitch : o->cin) != (o->out_pitch ? o->out_pitch : o->cout)))
+      return fail(UDP_ERR_ARG, "udp_conv2d_fused: activation + squeeze-excitation in place needs the same view for in and out");
   }
   if (o->kind == UDP_OP_SE_RES || o->kind == UDP_OP_PRM_GATE || o->kind == UDP_OP_PRM_DW9) {
     // the gates of RSN-18 "se + prm": `res` = the shortcut (optional) / -- / out_1; UDP_OP_PRM_DW9: `up0` = the channel gate's fp32 rows
@@ -1218,7 +1241,7 @@ static int conv2d_params(const udp_conv_op* o, int dtype, int n, const void* in,
   p.Cout = o->cout;
   p.CoutPad = o->cout_pad;
   p.relu = o->relu;
-  if (o->kind == UDP_OP_SE || o->kind == UDP_OP_GNORM || o->kind == UDP_OP_LNORM) {
+  if (o->kind == UDP_OP_SE || o->kind == UDP_OP_GNORM || o->kind == UDP_OP_LNORM || o->kind == UDP_OP_SE_ACT) {
     p.up_shift[0] = o->chain_cout;      // hidden width / real channels (se_validate, gnorm_validate, lnorm_validate: n_up == 0, n_out2 == 0)
   } else if (o->kind == UDP_OP_SE_RES || o->kind == UDP_OP_PRM_GATE) {
     p.up_shift[0] = o->kind == UDP_OP_SE_RES ? o->chain_cout : o->cin;      // hidden width (n_up == 0, n_out2 == 0)
@@ -1282,6 +1305,7 @@ static int conv2d_fused_impl(const udp_conv_op* o, int dtype, int n, const void*
                  : o->kind == UDP_OP_DECONV ? describe_deconv(p, dtype, &l)
                  : o->kind == UDP_OP_DWCONV ? describe_dwconv(p, dtype, o->ks, o->stride, &l)
                  : o->kind == UDP_OP_SE     ? describe_se(p, dtype, &l)
+                 : o->kind == UDP_OP_SE_ACT ? describe_se_act(p, dtype, &l)
                  : o->kind == UDP_OP_GNORM  ? describe_gnorm(p, dtype, &l)
                  : o->kind == UDP_OP_LINATTN ? describe_linattn(p, dtype, &l)
                  : o->kind == UDP_OP_LNORM  ? describe_lnorm(p, dtype, &l)

@@ -61,6 +61,7 @@ def mobilevitv2_spec(extra, num_joints=17, target_type="gaussian"):
 
 
 class MobileViTv2Program(ShuffleNetV2Program):
+    NAME = NAME
     """On ``program.Program`` through the ShuffleNetV2 planner, whose ``_pw`` / ``_dw`` helpers it uses."""
 
     def __init__(self, state_dict, spec, in_h, in_w, dtype="f32"):
@@ -164,23 +165,9 @@ class MobileViTv2Program(ShuffleNetV2Program):
             p = "backbone.layer_%d" % (li + 3)
             x, c = self._inverted_residual(p + ".0", x, c)
             x, c = self._mit_block(p + ".1", x, c, n_units)
-        w, b = self._fold("decoder.conv_compress")                      # linear: no BatchNorm, no activation (pixelshuffle.py:15-16)
-        if int(w.shape[1]) != c or c != DECODER_INPLANES[spec["model_size"]]:
-            raise ValueError("decoder.conv_compress expects %d input channels, the backbone ends with %d" % (int(w.shape[1]), c))
-        x = self._pw("decoder.conv_compress", x, w, b, False, cin_t=x.c)
-        for d, planes in enumerate(spec["architecture"]):               # DUC.py:23-28
-            q = "decoder.duc.%d" % d
-            w, b = self._fold(q + ".conv", q + ".bn")
-            cq = planes // 4
-            # PixelShuffle reads channel 4c + g for sub-pixel g = 2i + j: store it at g * cq + c (UDP_OP_PIXSHUF)
-            t = self._pw(q + ".conv", x, w, b, True, out_map=[(o % 4) * cq + o // 4 for o in range(planes)])
-            x = self._new(cq, 2 * t.h, 2 * t.w)
-            self._emit(_lib.UDP_OP_PIXSHUF, q + ".pixel_shuffle", t, x, ks=1, stride=1)
-        if (x.h, x.w) != (H // 4, W // 4):
-            raise ValueError("%s: heat-maps at %dx%d, expected %dx%d" % (NAME, x.h, x.w, H // 4, W // 4))
-        w, b = self._fold("final_layer")
-        self._pw("final_layer", x, w, b, False, to_output=True)
-        self.out_channels = self._ops[-1]["cout"]
+        if c != DECODER_INPLANES[spec["model_size"]]:
+            raise ValueError("%s: the decoder expects %d input channels, the backbone ends with %d" % (NAME, DECODER_INPLANES[spec["model_size"]], c))
+        self._ps_head(x, c)
         # accepted and unused: BatchNorm bookkeeping and the ImageNet classifier forward() never applies (mobilevitv2.py:1440-1444)
         self.unused_keys = unused_keys(sd)
         sd.used.update(self.unused_keys)

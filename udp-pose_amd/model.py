@@ -470,14 +470,18 @@ class PoseShuffleNetV2Hip(PoseNetHip):
     DTYPES = ("f32", "f16x2")
 
     def __init__(self, cfg, dtype="f32"):
-        from .shufflenet_plan import shufflenet_spec
         if dtype not in self.DTYPES:
             raise ValueError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
         super().__init__(cfg, dtype)
         self.extra = _get(cfg, "MODEL", "EXTRA")
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
-        self.spec = shufflenet_spec(self.extra, self.num_joints, self.target_type)   # NotImplementedError for 2.0x ...
+        self.spec = self._spec_of(self.extra, self.num_joints, self.target_type)   # NotImplementedError for 2.0x ...
+
+    @staticmethod
+    def _spec_of(extra, num_joints, target_type):
+        from .shufflenet_plan import shufflenet_spec
+        return shufflenet_spec(extra, num_joints, target_type)
 
     def param_shapes(self):
         from .synth_shufflenet import shufflenet_param_shapes
@@ -511,14 +515,18 @@ class PoseShuffleNetV2PlusHip(PoseNetHip):
     DTYPES = ("f32", "f16x2")
 
     def __init__(self, cfg, dtype="f32"):
-        from .shufflenet_plus_plan import shufflenet_plus_spec
         if dtype not in self.DTYPES:
             raise ValueError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
         super().__init__(cfg, dtype)
         self.extra = _get(cfg, "MODEL", "EXTRA")
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
-        self.spec = shufflenet_plus_spec(self.extra, self.num_joints, self.target_type)   # NotImplementedError for an unknown size ...
+        self.spec = self._spec_of(self.extra, self.num_joints, self.target_type)   # NotImplementedError for an unknown size ...
+
+    @staticmethod
+    def _spec_of(extra, num_joints, target_type):
+        from .shufflenet_plus_plan import shufflenet_plus_spec
+        return shufflenet_plus_spec(extra, num_joints, target_type)
 
     def param_shapes(self):
         from .synth_shufflenet_plus import shufflenet_plus_param_shapes
@@ -626,9 +634,131 @@ def get_pose_net_mobilevit(cfg, is_train, **kwargs):
     return PoseMobileViTHip(cfg, **kwargs)
 
 
+class PoseShuffleNetV2DeconvHip(PoseShuffleNetV2Hip):
+    """pose_shufflenetv2_10x (deep_hrnet/lib/models/pose_shufflenetv2_10x.py:22-97): the ShuffleNetV2 backbone of
+    ``PoseShuffleNetV2Hip`` with the deconv head of pose_resnet behind ``conv_last`` -- three ConvTranspose2d(4, 2, 1) +
+    BN + ReLU, ``final_layer``; spec keys NUM_DECONV_*, DECONV_WITH_BIAS, FINAL_CONV_KERNEL.  The same storage modes and
+    MODEL_SIZE refusals."""
+
+    NAME = "pose_shufflenetv2_10x"
+
+    @staticmethod
+    def _spec_of(extra, num_joints, target_type):
+        from .shufflenet_plan import shufflenet_deconv_spec
+        return shufflenet_deconv_spec(extra, num_joints, target_type)
+
+    def param_shapes(self):
+        from .synth_shufflenet import shufflenet_deconv_param_shapes
+        sp = self.spec
+        return shufflenet_deconv_param_shapes(model_size=sp["model_size"], num_joints=self.num_joints, target_type=self.target_type,
+                                              deconv_filters=sp["deconv_filters"], final_kernel=sp["final_kernel"],
+                                              deconv_with_bias=sp["deconv_with_bias"])
+
+
+def get_pose_net_shufflenetv2_deconv(cfg, is_train, **kwargs):
+    """pose_shufflenetv2_10x.py:100-109 (``get_pose_net``); inference only -- the weights come from ``load_state_dict``."""
+    return PoseShuffleNetV2DeconvHip(cfg, **kwargs)
+
+
+class PoseShuffleNetV2PlusDeconvHip(PoseShuffleNetV2PlusHip):
+    """pose_shufflenetv2_plus (deep_hrnet/lib/models/pose_shufflenetv2_plus.py:22-99): the ShuffleNetV2+ backbone of
+    ``PoseShuffleNetV2PlusHip`` with the deconv head of pose_resnet behind ``conv_last`` (1280 channels).  The same
+    storage modes and MODEL_SIZE refusal."""
+
+    NAME = "pose_shufflenetv2_plus"
+
+    @staticmethod
+    def _spec_of(extra, num_joints, target_type):
+        from .shufflenet_plus_plan import shufflenet_plus_deconv_spec
+        return shufflenet_plus_deconv_spec(extra, num_joints, target_type)
+
+    def param_shapes(self):
+        from .synth_shufflenet_plus import shufflenet_plus_deconv_param_shapes
+        sp = self.spec
+        return shufflenet_plus_deconv_param_shapes(model_size=sp["model_size"], num_joints=self.num_joints, target_type=self.target_type,
+                                                   deconv_filters=sp["deconv_filters"], final_kernel=sp["final_kernel"],
+                                                   deconv_with_bias=sp["deconv_with_bias"])
+
+
+def get_pose_net_shufflenetv2_plus_deconv(cfg, is_train, **kwargs):
+    """pose_shufflenetv2_plus.py:102-111 (``get_pose_net``); inference only -- the weights come from ``load_state_dict``."""
+    return PoseShuffleNetV2PlusDeconvHip(cfg, **kwargs)
+
+
+class PoseMobileNetV3PixelShuffleHip(PoseNetHip):
+    """pose_mobilenetv3_small_pixel_shuffle (deep_hrnet/lib/models/pose_mobilenetv3_small_pixel_shuffle.py:23-52:
+    torchvision's MobileNetV3-small ``features`` -- hard-swish, 3x3 / 5x5 depthwise convs, squeeze-excitation with
+    biases, BatchNorm eps 1e-3 --, the pixel-shuffle (DUC) decoder, ``final_layer``) inference through the same C ABI;
+    ``state_dict`` in the reference module's key format (``backbone.0.*``).  MODEL_SIZE 'large' is refused (the
+    reference cannot run it either).  Storage modes "f32" and "f16x2"."""
+
+    NAME = "pose_mobilenetv3_small_pixel_shuffle"
+    DTYPES = ("f32", "f16x2")
+
+    def __init__(self, cfg, dtype="f32"):
+        if dtype not in self.DTYPES:
+            raise NotImplementedError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
+        super().__init__(cfg, dtype)
+        self.extra = _get(cfg, "MODEL", "EXTRA")
+        self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
+        self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
+        self.spec = self._spec_of(self.extra, self.num_joints, self.target_type)   # NotImplementedError for 'large' ...
+
+    @staticmethod
+    def _spec_of(extra, num_joints, target_type):
+        from .mobilenetv3_plan import mobilenetv3_ps_spec
+        return mobilenetv3_ps_spec(extra, num_joints, target_type)
+
+    def param_shapes(self):
+        from .synth_mobilenetv3 import mobilenetv3_ps_param_shapes
+        sp = self.spec
+        return mobilenetv3_ps_param_shapes(num_joints=self.num_joints, target_type=self.target_type, start_channels=sp["start_channels"],
+                                           architecture=sp["architecture"], final_kernel=sp["final_kernel"])
+
+    def init_weights(self, pretrained=""):
+        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+
+    def _make_program(self, h, w):
+        from .mobilenetv3_plan import MobileNetV3Program
+        return MobileNetV3Program(self._sd, self.spec, h, w, self.dtype)
+
+
+def get_pose_net_mobilenetv3_pixel_shuffle(cfg, is_train, **kwargs):
+    """pose_mobilenetv3_small_pixel_shuffle.py:55-64 (``get_pose_net``); inference only -- the weights come from
+    ``load_state_dict`` (the reference downloads ImageNet weights under is_train; training is out of scope)."""
+    return PoseMobileNetV3PixelShuffleHip(cfg, **kwargs)
+
+
+class PoseMobileNetV3Hip(PoseMobileNetV3PixelShuffleHip):
+    """pose_mobilenetv3_small (deep_hrnet/lib/models/pose_mobilenetv3_small.py): the same backbone with the deconv head
+    of pose_resnet -- three ConvTranspose2d(4, 2, 1) + BN + ReLU, ``final_layer``."""
+
+    NAME = "pose_mobilenetv3_small"
+
+    @staticmethod
+    def _spec_of(extra, num_joints, target_type):
+        from .mobilenetv3_plan import mobilenetv3_deconv_spec
+        return mobilenetv3_deconv_spec(extra, num_joints, target_type)
+
+    def param_shapes(self):
+        from .synth_mobilenetv3 import mobilenetv3_deconv_param_shapes
+        sp = self.spec
+        return mobilenetv3_deconv_param_shapes(num_joints=self.num_joints, target_type=self.target_type, deconv_filters=sp["deconv_filters"],
+                                               final_kernel=sp["final_kernel"], deconv_with_bias=sp["deconv_with_bias"])
+
+
+def get_pose_net_mobilenetv3(cfg, is_train, **kwargs):
+    """pose_mobilenetv3_small.py (``get_pose_net``); inference only -- the weights come from ``load_state_dict``."""
+    return PoseMobileNetV3Hip(cfg, **kwargs)
+
+
 MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet,
           "pose_resnet_psa": get_pose_net_resnet_psa,
           "pose_shufflenetv2_10x_pixel_shuffle": get_pose_net_shufflenetv2,
           "pose_shufflenetv2_plus_pixel_shuffle": get_pose_net_shufflenetv2_plus,
           "pose_mobilevitv2_pixel_shuffle": get_pose_net_mobilevitv2,
-          "pose_mobilevit_pixel_shuffle": get_pose_net_mobilevit}
+          "pose_mobilevit_pixel_shuffle": get_pose_net_mobilevit,
+          "pose_shufflenetv2_10x": get_pose_net_shufflenetv2_deconv,
+          "pose_shufflenetv2_plus": get_pose_net_shufflenetv2_plus_deconv,
+          "pose_mobilenetv3_small_pixel_shuffle": get_pose_net_mobilenetv3_pixel_shuffle,
+          "pose_mobilenetv3_small": get_pose_net_mobilenetv3}

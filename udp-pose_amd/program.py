@@ -109,14 +109,15 @@ class Program:
         self._blob_size = off + len(arr_bytes)
         return off
 
-    def _fold(self, conv, bn=None, axis=0):
+    def _fold(self, conv, bn=None, axis=0, eps=BN_EPS):
         """``conv`` (+ its bias, if the state_dict has one) + BatchNorm(eval) ``bn`` folded in fp64 -> fp32 (weight, bias).
-        ``axis``: the weight's output-channel dimension (1 for a ConvTranspose2d's [cin, cout, k, k])."""
+        ``axis``: the weight's output-channel dimension (1 for a ConvTranspose2d's [cin, cout, k, k]); ``eps``: the
+        BatchNorm's (torchvision's MobileNetV3 backbone builds its norms with 1e-3)."""
         f64 = lambda k: self.sd[k].detach().to(torch.float64).cpu()
         w = f64(conv + ".weight")
         b = f64(conv + ".bias") if self.sd.get(conv + ".bias") is not None else torch.zeros(w.shape[axis], dtype=torch.float64)
         if bn is not None:
-            s = f64(bn + ".weight") / torch.sqrt(f64(bn + ".running_var") + BN_EPS)
+            s = f64(bn + ".weight") / torch.sqrt(f64(bn + ".running_var") + eps)
             w = w * s.reshape([-1 if d == axis else 1 for d in range(4)])
             b = (b - f64(bn + ".running_mean")) * s + f64(bn + ".bias")
         return w.to(torch.float32), b.to(torch.float32)
@@ -244,6 +245,41 @@ class Program:
                    hout=ho, wout=wo, res=res, ups=list(ups), w_off=w_off, b_off=b_off, group=group, wfmt=int(ws), wexp=wexp,
                    **views)
         return (out, z) if chain is not None else out
+
+    def _deconv(self, x, d):
+        """deconv_layers[3d] (ConvTranspose2d, [cin, cout, 4, 4], bias if DECONV_WITH_BIAS) + [3d+1] (BatchNorm) + ReLU:
+        the BatchNorm scale folds along dim 1 (the output channels), the deconv bias into the BatchNorm bias."""
+        q = "deconv_layers.%d" % (3 * d)
+        w, b = self._fold(q, "deconv_layers.%d" % (3 * d + 1), axis=1)
+        cin, cout = int(w.shape[0]), int(w.shape[1])
+        if cin != x.c:
+            raise ValueError("%s expects %d input channels, got %d" % (q, cin, x.c))
+        cout_pad = _round_up(cout, 32)
+        from .f16x2 import deconv_phase_taps, pack_deconv_weights_ws
+        wexp = 0
+        if self.dtype == "f16x2":
+            packed, wexp = pack_deconv_weights_ws(w, cout_pad)
+            w_off = self._put(packed.numpy().tobytes())
+        else:
+            w_off = self._put(encode_weights(deconv_phase_taps(w, cout_pad), self.dtype))
+        bp = torch.zeros(cout_pad, dtype=torch.float32)
+        bp[:cout] = b
+        out = self._new(cout, 2 * x.h, 2 * x.w)
+        self._emit(_lib.UDP_OP_DECONV, q, x, out, ks=4, stride=2, relu=1, w_off=w_off,
+                   b_off=self._put(bp.numpy().tobytes()), wfmt=int(self.dtype == "f16x2"), wexp=wexp)
+        return out
+
+    def _deconv_head(self, x, name, n_deconv):
+        """The SimpleBaseline head every deconv-head net of the reference shares (pose_resnet.py:155-193, :128-136;
+        pose_shufflenetv2_10x.py, pose_shufflenetv2_plus.py and pose_mobilenetv3_small.py repeat it): ``n_deconv`` x
+        [ConvTranspose2d(4, 2, 1) + BatchNorm + ReLU] = one UDP_OP_DECONV each, then the biased 1x1 / 3x3
+        ``final_layer`` writing the NCHW fp32 heat-maps.  Sets ``out_channels``."""
+        for d in range(n_deconv):
+            x = self._deconv(x, d)
+        if (x.h, x.w) != (self.in_h // 4, self.in_w // 4):
+            raise ValueError("%s: heat-maps at %dx%d, expected %dx%d" % (name, x.h, x.w, self.in_h // 4, self.in_w // 4))
+        self._conv(x, "final_layer", None, relu=False, to_output=True)
+        self.out_channels = self._ops[-1]["cout"]
 
     def _psa(self, x, p):
         """PSA_s (PSA.py:190-269) as POOL -> MLP -> SCALE -> 1x1 conv (theta) -> SP; see csrc/psa.hip."""

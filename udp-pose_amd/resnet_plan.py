@@ -12,7 +12,7 @@ BasicBlocks with a polarized self-attention block after bn1.
 import torch
 
 from . import _lib
-from .program import Program, _round_up, encode_weights
+from .program import Program
 
 # resnet_spec of pose_resnet.py:254-260 (Bottleneck depths only; BasicBlock 18 / 34 ship in no YAML)
 RESNET_LAYERS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -37,20 +37,20 @@ def pose_resnet_spec(extra):
     return dict(_head_spec(extra), layers=RESNET_LAYERS[num_layers])
 
 
-def _head_spec(extra):
-    """The deconv head / final layer part of the spec, with its refusals."""
+def _head_spec(extra, name="pose_resnet"):
+    """The deconv head / final layer part of the spec, with its refusals (``name``: how the messages call the net)."""
     nd = int(_get(extra, "NUM_DECONV_LAYERS", 3))
     filters = [int(f) for f in _get(extra, "NUM_DECONV_FILTERS", [256] * nd)]
     kernels = [int(k) for k in _get(extra, "NUM_DECONV_KERNELS", [4] * nd)]
     if nd != 3 or len(filters) != nd or len(kernels) != nd:
-        raise NotImplementedError("pose_resnet: NUM_DECONV_LAYERS=%d (filters %s, kernels %s): only 3 deconv layers "
-                                  "(heat-maps at 1/4 of the input) are supported" % (nd, filters, kernels))
+        raise NotImplementedError("%s: NUM_DECONV_LAYERS=%d (filters %s, kernels %s): only 3 deconv layers "
+                                  "(heat-maps at 1/4 of the input) are supported" % (name, nd, filters, kernels))
     if any(k != 4 for k in kernels):
-        raise NotImplementedError("pose_resnet: NUM_DECONV_KERNELS=%s: only ConvTranspose2d(k=4, s=2, p=1) has a kernel "
-                                  "(kernels 2 / 3 ship in no reference YAML)" % (kernels,))
+        raise NotImplementedError("%s: NUM_DECONV_KERNELS=%s: only ConvTranspose2d(k=4, s=2, p=1) has a kernel "
+                                  "(kernels 2 / 3 ship in no reference YAML)" % (name, kernels))
     final_kernel = int(_get(extra, "FINAL_CONV_KERNEL", 1))
     if final_kernel not in (1, 3):
-        raise NotImplementedError("pose_resnet: FINAL_CONV_KERNEL=%d (1 or 3)" % final_kernel)
+        raise NotImplementedError("%s: FINAL_CONV_KERNEL=%d (1 or 3)" % (name, final_kernel))
     return dict(deconv_filters=tuple(filters), final_kernel=final_kernel,
                 deconv_with_bias=bool(_get(extra, "DECONV_WITH_BIAS", False)))
 
@@ -94,29 +94,6 @@ class PoseResNetProgram(Program):
     def consumed_keys(self):
         return set(self.sd.used)
 
-    def _deconv(self, x, d):
-        """deconv_layers[3d] (ConvTranspose2d, [cin, cout, 4, 4], bias if DECONV_WITH_BIAS) + [3d+1] (BatchNorm) + ReLU:
-        the BatchNorm scale folds along dim 1 (the output channels), the deconv bias into the BatchNorm bias."""
-        q = "deconv_layers.%d" % (3 * d)
-        w, b = self._fold(q, "deconv_layers.%d" % (3 * d + 1), axis=1)
-        cin, cout = int(w.shape[0]), int(w.shape[1])
-        if cin != x.c:
-            raise ValueError("%s expects %d input channels, got %d" % (q, cin, x.c))
-        cout_pad = _round_up(cout, 32)
-        from .f16x2 import deconv_phase_taps, pack_deconv_weights_ws
-        wexp = 0
-        if self.dtype == "f16x2":
-            packed, wexp = pack_deconv_weights_ws(w, cout_pad)
-            w_off = self._put(packed.numpy().tobytes())
-        else:
-            w_off = self._put(encode_weights(deconv_phase_taps(w, cout_pad), self.dtype))
-        bp = torch.zeros(cout_pad, dtype=torch.float32)
-        bp[:cout] = b
-        out = self._new(cout, 2 * x.h, 2 * x.w)
-        self._emit(_lib.UDP_OP_DECONV, q, x, out, ks=4, stride=2, relu=1, w_off=w_off,
-                   b_off=self._put(bp.numpy().tobytes()), wfmt=int(self.dtype == "f16x2"), wexp=wexp)
-        return out
-
     def _block(self, x, p, stride):
         """Bottleneck.forward (:82-100)."""
         a = self._conv(x, p + ".conv1", p + ".bn1")
@@ -137,12 +114,7 @@ class PoseResNetProgram(Program):
         for li, nblk in enumerate(self.spec["layers"], start=1):          # _make_layer (:138-153)
             for k in range(nblk):
                 x = self._block(x, "layer%d.%d" % (li, k), 2 if (li > 1 and k == 0) else 1)
-        for d in range(len(self.spec["deconv_filters"])):
-            x = self._deconv(x, d)
-        if (x.h, x.w) != (H // 4, W // 4):
-            raise ValueError("pose_resnet: heat-maps at %dx%d, expected %dx%d" % (x.h, x.w, H // 4, W // 4))
-        self._conv(x, "final_layer", None, relu=False, to_output=True)
-        self.out_channels = self._ops[-1]["cout"]
+        self._deconv_head(x, "pose_resnet", len(self.spec["deconv_filters"]))
         for k in sd:
             if k.endswith("num_batches_tracked"):
                 sd.used.add(k)                                              # BatchNorm bookkeeping, not an operand

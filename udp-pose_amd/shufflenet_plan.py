@@ -23,8 +23,8 @@ import os
 import torch
 
 from . import _lib
-from .program import Program, _round_up
-from .resnet_plan import _Tracked, _get
+from .program import BN_EPS, Program, _round_up
+from .resnet_plan import _Tracked, _get, _head_spec
 from .synth_shufflenet import DECODER_INPLANES, STAGE_OUT_CHANNELS, shufflenet_units
 
 
@@ -52,6 +52,20 @@ def shufflenet_spec(extra, num_joints=17, target_type="gaussian"):
                 out_channels=int(num_joints) * (3 if target_type == "offset" else 1))
 
 
+def shufflenet_deconv_spec(extra, num_joints=17, target_type="gaussian"):
+    """MODEL.EXTRA of a pose_shufflenetv2_10x YAML (the deconv-head sibling, pose_shufflenetv2_10x.py:22-97) ->
+    dict(model_size, deconv_filters, final_kernel, deconv_with_bias, out_channels).  The MODEL_SIZE refusals of the
+    pixel-shuffle net (the head is built for 1024 channels here too, :25) and the head refusals of ``_head_spec``."""
+    size = str(_get(extra, "MODEL_SIZE", "1.0x"))
+    if size == "2.0x":
+        raise NotImplementedError("pose_shufflenetv2_10x MODEL_SIZE='2.0x': the reference itself cannot run it -- conv_last has "
+                                  "2048 channels but the deconv head is built for %d (pose_shufflenetv2_10x.py:25)" % DECODER_INPLANES)
+    if size not in STAGE_OUT_CHANNELS:
+        raise NotImplementedError("pose_shufflenetv2_10x MODEL_SIZE=%r (one of '0.5x', '1.0x', '1.5x')" % size)
+    return dict(_head_spec(extra, "pose_shufflenetv2_10x"), model_size=size,
+                out_channels=int(num_joints) * (3 if target_type == "offset" else 1))
+
+
 def _halves(r):
     """Positions of the 2r logical channels of a unit tensor: (positions, cp)."""
     cp = _round_up(r, 32)
@@ -59,6 +73,7 @@ def _halves(r):
 
 
 class ShuffleNetV2Program(Program):
+    NAME = "pose_shufflenetv2"
     DW_KERNELS = (3,)
 
     def __init__(self, state_dict, spec, in_h, in_w, dtype="f32"):
@@ -109,11 +124,11 @@ class ShuffleNetV2Program(Program):
                    hout=x.h, wout=x.w, w_off=w_off, b_off=b_off, wfmt=int(ws), wexp=wexp, **views)
         return out
 
-    def _dw(self, conv, bn, x, cin, pos, stride, into=None, passthrough=None, act=0):
+    def _dw(self, conv, bn, x, cin, pos, stride, into=None, passthrough=None, act=0, eps=BN_EPS):
         """Depthwise k x k conv (k = 3, or 5 / 7 in the ShuffleNetV2+ planner) + BatchNorm on the first ``cin`` stored
         channels of ``x``; ``pos[j]``: where logical channel j of the [C,1,k,k] weight sits.  ``into = (tensor, coff)``; ``passthrough = (src, dst, r)``: the
-        x_proj copy of a stride-1 unit (include/udp_pose_hip.h, UDP_OP_DWCONV); ``act``: the activation code."""
-        w, b = self._fold(conv, bn)
+        x_proj copy of a stride-1 unit (include/udp_pose_hip.h, UDP_OP_DWCONV); ``act``: the activation code; ``eps``: the BatchNorm's."""
+        w, b = self._fold(conv, bn, eps=eps)
         ks = int(w.shape[2])
         if tuple(w.shape[1:]) != (1, ks, ks) or ks not in self.DW_KERNELS or w.shape[0] != len(pos):
             raise ValueError("%s.weight must be [%d,1,k,k], k one of %s" % (conv, len(pos), self.DW_KERNELS))
@@ -139,9 +154,46 @@ class ShuffleNetV2Program(Program):
                    w_off=self._put(wp.numpy().tobytes()), b_off=self._put(bp.numpy().tobytes()), **views)
         return out
 
+    def _ps_head(self, x, c=None):
+        """The pixel-shuffle head every ``*_pixel_shuffle`` net of the reference shares (decoders/pixelshuffle.py:15-31,
+        DUC.py:15-28): the linear 1x1 ``conv_compress`` on the ``c`` real channels of ``x`` (default: all it stores),
+        three DUC blocks = 3x3 conv + BN + ReLU + PixelShuffle(2), and the biased ``final_layer`` writing the NCHW fp32
+        heat-maps.  Sets ``out_channels``."""
+        w, b = self._fold("decoder.conv_compress")                      # linear: no BatchNorm, no activation (pixelshuffle.py:15-16)
+        c = x.c if c is None else c
+        if int(w.shape[1]) != c:
+            raise ValueError("decoder.conv_compress expects %d input channels, the backbone ends with %d" % (int(w.shape[1]), c))
+        x = self._pw("decoder.conv_compress", x, w, b, False, cin_t=x.c)
+        for d, planes in enumerate(self.spec["architecture"]):          # DUC.py:23-28
+            q = "decoder.duc.%d" % d
+            w, b = self._fold(q + ".conv", q + ".bn")
+            cq = planes // 4
+            # PixelShuffle reads channel 4c + g for sub-pixel g = 2i + j: store it at g * cq + c (UDP_OP_PIXSHUF)
+            t = self._pw(q + ".conv", x, w, b, True, out_map=[(o % 4) * cq + o // 4 for o in range(planes)])
+            x = self._new(cq, 2 * t.h, 2 * t.w)
+            self._emit(_lib.UDP_OP_PIXSHUF, q + ".pixel_shuffle", t, x, ks=1, stride=1)
+        if (x.h, x.w) != (self.in_h // 4, self.in_w // 4):
+            raise ValueError("%s: heat-maps at %dx%d, expected %dx%d" % (self.NAME, x.h, x.w, self.in_h // 4, self.in_w // 4))
+        w, b = self._fold("final_layer")
+        self._pw("final_layer", x, w, b, False, to_output=True)
+        self.out_channels = self._ops[-1]["cout"]
+
+    def _head(self, x):
+        """Behind the backbone: the deconv head when the spec carries ``deconv_filters`` (the nets without
+        ``_pixel_shuffle`` in their name), the pixel-shuffle head otherwise."""
+        if "deconv_filters" in self.spec:
+            self._deconv_head(x, self.NAME, len(self.spec["deconv_filters"]))
+        else:
+            self._ps_head(x)
+
     # ------------------------------------------------------------------ the net
     def _build(self):
         self.sd = _Tracked(self.sd)
+        self._head(self._backbone())
+        self._mark_unused()
+
+    def _backbone(self):
+        """Stem to ``conv_last``: returns its output tensor."""
         sd, spec = self.sd, self.spec
         H, W = self.in_h, self.in_w
         # stem: the kernel computes 64 output channels; the real ones first, zero weights and bias behind them
@@ -191,27 +243,12 @@ class ShuffleNetV2Program(Program):
                 x = y
             pos = npos
         w, b = self._fold("backbone.conv_last.0", "backbone.conv_last.1")
-        x = self._pw("backbone.conv_last.0", x, w, b, True, in_map=pos, cin_t=x.c)
-        w, b = self._fold("decoder.conv_compress")                      # linear: no BatchNorm, no ReLU (pixelshuffle.py:15-16)
-        if int(w.shape[1]) != x.c:
-            raise ValueError("decoder.conv_compress expects %d input channels, conv_last has %d" % (int(w.shape[1]), x.c))
-        x = self._pw("decoder.conv_compress", x, w, b, False)
-        for d, planes in enumerate(spec["architecture"]):               # DUC.py:23-28
-            q = "decoder.duc.%d" % d
-            w, b = self._fold(q + ".conv", q + ".bn")
-            cq = planes // 4
-            # PixelShuffle reads channel 4c + g for sub-pixel g = 2i + j: store it at g * cq + c (UDP_OP_PIXSHUF)
-            t = self._pw(q + ".conv", x, w, b, True, out_map=[(o % 4) * cq + o // 4 for o in range(planes)])
-            x = self._new(cq, 2 * t.h, 2 * t.w)
-            self._emit(_lib.UDP_OP_PIXSHUF, q + ".pixel_shuffle", t, x, ks=1, stride=1)
-        if (x.h, x.w) != (H // 4, W // 4):
-            raise ValueError("pose_shufflenetv2: heat-maps at %dx%d, expected %dx%d" % (x.h, x.w, H // 4, W // 4))
-        w, b = self._fold("final_layer")
-        self._pw("final_layer", x, w, b, False, to_output=True)
-        self.out_channels = self._ops[-1]["cout"]
-        for k in sd:
+        return self._pw("backbone.conv_last.0", x, w, b, True, in_map=pos, cin_t=x.c)
+
+    def _mark_unused(self):
+        for k in self.sd:
             if k.endswith("num_batches_tracked") or k == "backbone.classifier.0.weight":
-                sd.used.add(k)              # BatchNorm bookkeeping / the ImageNet classifier forward() never applies (:160-165)
+                self.sd.used.add(k)              # BatchNorm bookkeeping / the ImageNet classifier forward() never applies (:160-165)
 
     def macs_per_image(self):
         return super().macs_per_image() + sum(op["ks"] ** 2 * op["cout"] * op["hout"] * op["wout"] for op in self._ops

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .program import _round_up
-from .resnet_plan import _Tracked, _get
+from .resnet_plan import _get, _head_spec
 from .shufflenet_plan import ShuffleNetV2Program, _halves
 from .synth_shufflenet_plus import DECODER_INPLANES, STAGE_OUT_CHANNELS, shufflenet_plus_units, unused_keys
 
@@ -51,7 +51,19 @@ def shufflenet_plus_spec(extra, num_joints=17, target_type="gaussian"):
                 out_channels=int(num_joints) * (3 if target_type == "offset" else 1))
 
 
+def shufflenet_plus_deconv_spec(extra, num_joints=17, target_type="gaussian"):
+    """MODEL.EXTRA of a pose_shufflenetv2_plus YAML (the deconv-head sibling, pose_shufflenetv2_plus.py:22-99) ->
+    dict(model_size, deconv_filters, final_kernel, deconv_with_bias, out_channels): the MODEL_SIZE refusal of the
+    pixel-shuffle net and the head refusals of ``resnet_plan._head_spec``."""
+    size = str(_get(extra, "MODEL_SIZE", "Small"))
+    if size not in STAGE_OUT_CHANNELS:
+        raise NotImplementedError("pose_shufflenetv2_plus MODEL_SIZE=%r (one of 'Small', 'Medium', 'Large')" % size)
+    return dict(_head_spec(extra, "pose_shufflenetv2_plus"), model_size=size,
+                out_channels=int(num_joints) * (3 if target_type == "offset" else 1))
+
+
 class ShuffleNetV2PlusProgram(ShuffleNetV2Program):
+    NAME = "pose_shufflenetv2_plus"
     DW_KERNELS = (3, 5, 7)
 
     def __init__(self, state_dict, spec, in_h, in_w, dtype="f32"):
@@ -78,8 +90,8 @@ class ShuffleNetV2PlusProgram(ShuffleNetV2Program):
                    chain_cout=hid, w_off=self._put(block.numpy().tobytes()))
 
     # ------------------------------------------------------------------ the net
-    def _build(self):
-        self.sd = _Tracked(self.sd)
+    def _backbone(self):
+        """Stem to ``conv_last``: returns its output tensor (``_build``, ``_head``: shufflenet_plan.ShuffleNetV2Program)."""
         sd, spec = self.sd, self.spec
         H, W = self.in_h, self.in_w
         HS = _lib.UDP_ACT_HSWISH
@@ -152,26 +164,14 @@ class ShuffleNetV2PlusProgram(ShuffleNetV2Program):
             x, pos = y, npos
         w, b = self._fold("backbone.conv_last.0", "backbone.conv_last.1")
         x = self._pw("backbone.conv_last.0", x, w, b, HS, in_map=pos, cin_t=x.c)
-        w, b = self._fold("decoder.conv_compress")                      # linear: no BatchNorm, no activation (pixelshuffle.py:15-16)
-        if int(w.shape[1]) != x.c or x.c != DECODER_INPLANES:
-            raise ValueError("decoder.conv_compress expects %d input channels, conv_last has %d" % (int(w.shape[1]), x.c))
-        x = self._pw("decoder.conv_compress", x, w, b, False)
-        for d, planes in enumerate(spec["architecture"]):               # DUC.py:23-28
-            q = "decoder.duc.%d" % d
-            w, b = self._fold(q + ".conv", q + ".bn")
-            cq = planes // 4
-            # PixelShuffle reads channel 4c + g for sub-pixel g = 2i + j: store it at g * cq + c (UDP_OP_PIXSHUF)
-            t = self._pw(q + ".conv", x, w, b, True, out_map=[(o % 4) * cq + o // 4 for o in range(planes)])
-            x = self._new(cq, 2 * t.h, 2 * t.w)
-            self._emit(_lib.UDP_OP_PIXSHUF, q + ".pixel_shuffle", t, x, ks=1, stride=1)
-        if (x.h, x.w) != (H // 4, W // 4):
-            raise ValueError("%s: heat-maps at %dx%d, expected %dx%d" % (NAME, x.h, x.w, H // 4, W // 4))
-        w, b = self._fold("final_layer")
-        self._pw("final_layer", x, w, b, False, to_output=True)
-        self.out_channels = self._ops[-1]["cout"]
+        if x.c != DECODER_INPLANES:
+            raise ValueError("%s: the head expects %d input channels, conv_last has %d" % (self.NAME, DECODER_INPLANES, x.c))
+        return x
+
+    def _mark_unused(self):
         # accepted and unused: BatchNorm bookkeeping and the ImageNet tail forward() never applies (shufflenetv2_plus.py:324-331)
-        self.unused_keys = unused_keys(sd)
-        sd.used.update(self.unused_keys)
+        self.unused_keys = unused_keys(self.sd)
+        self.sd.used.update(self.unused_keys)
 
     def macs_per_image(self):
         # + the two small products of every squeeze-excitation layer (its pool and scale are not counted)

@@ -41,8 +41,7 @@ def shufflenet_units(model_size):
     return units
 
 
-def shufflenet_param_shapes(model_size="1.0x", num_joints=17, target_type="gaussian", start_channels=256,
-                            architecture=(512, 256, 128), final_kernel=1):
+def _backbone_shapes(model_size):
     ch = STAGE_OUT_CHANNELS[model_size]
     s = OrderedDict()
     s["backbone.first_conv.0.weight"] = (ch[0], 3, 3, 3)
@@ -63,6 +62,12 @@ def shufflenet_param_shapes(model_size="1.0x", num_joints=17, target_type="gauss
     s["backbone.conv_last.0.weight"] = (ch[4], ch[3], 1, 1)
     _bn(s, "backbone.conv_last.1", ch[4])
     s["backbone.classifier.0.weight"] = (N_CLASS, ch[4])
+    return s
+
+
+def shufflenet_param_shapes(model_size="1.0x", num_joints=17, target_type="gaussian", start_channels=256,
+                            architecture=(512, 256, 128), final_kernel=1):
+    s = _backbone_shapes(model_size)
     s["decoder.conv_compress.weight"] = (start_channels, DECODER_INPLANES, 1, 1)
     cin = start_channels
     for d, planes in enumerate(architecture):
@@ -73,6 +78,69 @@ def shufflenet_param_shapes(model_size="1.0x", num_joints=17, target_type="gauss
     s["final_layer.weight"] = (nout, cin, final_kernel, final_kernel)
     s["final_layer.bias"] = (nout,)
     return s
+
+
+def _final(s, cin, num_joints, target_type, final_kernel):
+    nout = num_joints * (3 if target_type == "offset" else 1)
+    s["final_layer.weight"] = (nout, cin, final_kernel, final_kernel)
+    s["final_layer.bias"] = (nout,)
+    return s
+
+
+def deconv_head_shapes(s, inplanes, num_joints=17, target_type="gaussian", deconv_filters=(256, 256, 256), final_kernel=1,
+                       deconv_with_bias=False):
+    """``deconv_layers`` ([ConvTranspose2d(4, 2, 1), BatchNorm, ReLU] x n: indices 3d, 3d + 1) and ``final_layer``
+    appended to ``s`` -- the head of pose_resnet that the deconv-head nets repeat."""
+    cin = inplanes
+    for d, planes in enumerate(deconv_filters):
+        s["deconv_layers.%d.weight" % (3 * d)] = (cin, planes, 4, 4)
+        if deconv_with_bias:
+            s["deconv_layers.%d.bias" % (3 * d)] = (planes,)
+        _bn(s, "deconv_layers.%d" % (3 * d + 1), planes)
+        cin = planes
+    return _final(s, cin, num_joints, target_type, final_kernel)
+
+
+def shufflenet_deconv_param_shapes(model_size="1.0x", num_joints=17, target_type="gaussian", deconv_filters=(256, 256, 256),
+                                   final_kernel=1, deconv_with_bias=False):
+    """pose_shufflenetv2_10x (pose_shufflenetv2_10x.py:22-97): the same backbone, the deconv head behind ``conv_last``."""
+    return deconv_head_shapes(_backbone_shapes(model_size), DECODER_INPLANES, num_joints, target_type, deconv_filters, final_kernel,
+                              deconv_with_bias)
+
+
+def seeded_state_dict(shapes, seed, calib=None, final_scale=1.0):
+    """Seeded weights for a shape table: convs ~ N(0, 2 / fan_in), BatchNorm weight ~ U(0.5, 1), biases ~ N(0, 0.05),
+    running statistics 0 / 1 unless ``calib`` ({key: array}) supplies them; the head is multiplied by ``final_scale``.
+    (The draws of synth_shufflenet.synth_shufflenet_state_dict, in the table's order.)"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sd = OrderedDict()
+    for k, shape in shapes.items():
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0, dtype=torch.long)
+        elif len(shape) == 4:
+            fan = shape[1] * shape[2] * shape[3]
+            sd[k] = torch.from_numpy((rng.standard_normal(shape) * np.sqrt(2.0 / fan)).astype(np.float32))
+        elif len(shape) == 2:
+            sd[k] = torch.from_numpy((rng.standard_normal(shape) * 0.01).astype(np.float32))
+        elif k.endswith(".weight"):
+            sd[k] = torch.from_numpy(rng.uniform(0.5, 1.0, shape).astype(np.float32))
+        elif k.endswith(".bias"):
+            sd[k] = torch.from_numpy((rng.standard_normal(shape) * 0.05).astype(np.float32))
+        elif k.endswith("running_var"):
+            sd[k] = torch.ones(shape)
+        else:
+            sd[k] = torch.zeros(shape)
+    if calib:
+        for k, v in calib.items():
+            sd[k] = torch.from_numpy(np.asarray(v, dtype=np.float32).copy())
+    sd["final_layer.weight"] = sd["final_layer.weight"] * float(final_scale)
+    sd["final_layer.bias"] = sd["final_layer.bias"] * float(final_scale)
+    return sd
+
+
+def synth_shufflenet_deconv_state_dict(seed=7, calib=None, final_scale=1.0, **kw):
+    """``synth_shufflenet_state_dict`` for pose_shufflenetv2_10x."""
+    return seeded_state_dict(shufflenet_deconv_param_shapes(**kw), seed, calib, final_scale)
 
 
 def synth_shufflenet_state_dict(seed=7, calib=None, final_scale=1.0, **kw):

@@ -12,7 +12,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .synth_shufflenet import _bn
+from .synth_shufflenet import _bn, deconv_head_shapes, seeded_state_dict
 
 # ShuffleNetV2_Plus.stage_out_channels[1:] (shufflenetv2_plus.py:247-252) and stage_repeats (:246)
 STAGE_OUT_CHANNELS = {"Small": (16, 36, 104, 208, 416, 1280), "Medium": (16, 48, 128, 256, 512, 1280),
@@ -47,8 +47,7 @@ def _se(s, name, c):
     s[name + ".SE_opr.4.weight"] = (c, c // 4, 1, 1)
 
 
-def shufflenet_plus_param_shapes(model_size="Small", num_joints=17, target_type="gaussian", start_channels=256,
-                                 architecture=(512, 256, 128), final_kernel=1):
+def _backbone_shapes(model_size):
     ch = STAGE_OUT_CHANNELS[model_size]
     s = OrderedDict()
     s["backbone.first_conv.0.weight"] = (ch[0], 3, 3, 3)
@@ -86,6 +85,24 @@ def shufflenet_plus_param_shapes(model_size="Small", num_joints=17, target_type=
     _se(s, "backbone.LastSE", ch[5])
     s["backbone.fc.0.weight"] = (ch[5], ch[5])
     s["backbone.classifier.0.weight"] = (N_CLASS, ch[5])
+    return s
+
+
+def shufflenet_plus_deconv_param_shapes(model_size="Small", num_joints=17, target_type="gaussian", deconv_filters=(256, 256, 256),
+                                        final_kernel=1, deconv_with_bias=False):
+    """pose_shufflenetv2_plus (pose_shufflenetv2_plus.py:22-99): the same backbone, the deconv head behind ``conv_last``."""
+    return deconv_head_shapes(_backbone_shapes(model_size), DECODER_INPLANES, num_joints, target_type, deconv_filters, final_kernel,
+                              deconv_with_bias)
+
+
+def synth_shufflenet_plus_deconv_state_dict(seed=7, calib=None, final_scale=1.0, **kw):
+    """``synth_shufflenet_plus_state_dict`` for pose_shufflenetv2_plus."""
+    return seeded_state_dict(shufflenet_plus_deconv_param_shapes(**kw), seed, calib, final_scale)
+
+
+def shufflenet_plus_param_shapes(model_size="Small", num_joints=17, target_type="gaussian", start_channels=256,
+                                 architecture=(512, 256, 128), final_kernel=1):
+    s = _backbone_shapes(model_size)
     s["decoder.conv_compress.weight"] = (start_channels, DECODER_INPLANES, 1, 1)
     cin = start_channels
     for d, planes in enumerate(architecture):
