@@ -576,11 +576,16 @@ int udp_oks_nms(const float* kpts, const double* areas, const double* box_scores
  *   w_fwd   [ks*ks][cout_pad=ceil32(cout)][cin_k=ceil16(cin)]                      (forward)
  *   w_dgrad [ks*ks][ceil32(cin)][ceil16(cout)], taps mirrored, Cin/Cout swapped  (input gradient;
  *           may be NULL).  conv2d backward w.r.t. the input of a stride-1 conv is
- *   udp_conv2d_fused(dy, w_dgrad); for stride 2 apply it to udp_zero_stuff2(dy). */
+ *   udp_conv2d_fused(dy, w_dgrad); for stride 2 apply it to udp_zero_stuff2(dy).
+ * ks in {1, 3, 7}: that; ks 7 is the stem of pose_resnet.py:112 (w_dgrad NULL: the image needs no gradient).
+ * ks == 4 is ConvTranspose2d(4, 2, 1) (pose_resnet.py:155-193), fp32 only: w is the module's [cin][cout][4][4] and
+ *   w_fwd   [16][ceil32(cout)][cin], entry 4*(2a+b) + 2t+u = w[ci][co][3-a-2t][3-b-2u]  (UDP_OP_DECONV, wfmt 0; cin % 16 == 0)
+ *   w_dgrad [16][ceil32(cin)][ceil16(cout)], entry 4*ky+kx = w[ci][co][ky][kx], zero filled  (udp_deconv4s2_dgrad; may be NULL) */
 int udp_pack_conv_weights(const float* w, int cout, int cin, int ks, int dtype, void* w_fwd,
                           void* w_dgrad, void* stream);
 /* The same for every conv of a model in one launch: a device array of n descriptors (shapes are
- * validated by the host that builds the table; ks in {1,3}). */
+ * validated by the host that builds the table; ks in {1,3,7}).  reserved == 1 marks a transposed conv (ks 4): w, cout,
+ * cin and both layouts as udp_pack_conv_weights(ks = 4) documents them; reserved == 0 everywhere else. */
 typedef struct udp_pack_desc {
   const float* w;
   void* w_fwd;
@@ -593,7 +598,12 @@ int udp_zero_stuff2(const void* dy, int n, int h, int w, int c, int dtype, void*
 /* dW[co][ci][ky][kx] (+)= sum_{n,y,x} dy[n,y,x,co] * x[n, y*s+ky-ks/2, x*s+kx-ks/2, ci]
  * (torch.nn.functional.conv2d backward w.r.t. weight).  x: [n,hin,win,cin_k], dy: [n,hout,wout,cout_k].
  * workspace: split-K partials, at least ks*ks*cout*cin*4 bytes (udp_conv2d_wgrad_workspace_bytes
- * suggests a size that keeps the chip full). */
+ * suggests a size that keeps the chip full).
+ * (ks, padding) is one of (1, 0), (3, 1), (7, 3) -- the stem of pose_resnet.py:112, stride 2, cin 3 in cin_k 16 -- and
+ * (4, 1).  ks == 4 is the weight gradient of ConvTranspose2d(4, 2, 1) (pose_resnet.py:155-193) with the roles swapped:
+ * `x` is the gradient of its OUTPUT [n,2h,2w,cin_k], `dy` its INPUT [n,h,w,cout_k], cout / cin the module's input /
+ * output channels, and dW [cout][cin][4][4] is then ConvTranspose2d.weight's own layout; it needs stride == 2,
+ * hin == 2*hout and win == 2*wout (anything else: UDP_ERR_ARG).  ks 4 and 7 are fp32 only (UDP_ERR_UNSUPPORTED in bf16). */
 size_t udp_conv2d_wgrad_workspace_bytes(int cout, int cin, int ks);
 int udp_conv2d_wgrad(const void* x, const void* dy, int n, int hin, int win, int cin_k, int hout,
                      int wout, int cout_k, int ks, int stride, int cout, int cin, int dtype, float* dw,
@@ -760,6 +770,36 @@ int udp_adam_step(float* p, const float* g, float* m, float* v, int64_t count, f
 int udp_adam_coefficients(float lr, float beta1, float beta2, int step, float* coef_host);
 int udp_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t count, float beta1, float beta2,
                       float eps, const float* coef_dev, float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Training of pose_resnet (SimpleBaseline, deep_hrnet/lib/models/pose_resnet.py;
+ * recipe experiments/coco/resnet/res50_256x192_d256x3_adam_lr1e-3.yaml): the ops
+ * its graph has beyond the HRNet step above.  fp32 only (UDP_F32; anything else
+ * is UDP_ERR_UNSUPPORTED).  Symbols only: UDP_POSE_ABI_VERSION stays as it is.
+ * The weight gradients of the transposed conv and of the stem are
+ * udp_conv2d_wgrad with ks 4 / 7; their packed operands come from
+ * udp_pack_conv_weights(_batch).
+ * ------------------------------------------------------------------------- */
+/* Input gradient of ConvTranspose2d(4, 2, 1) (pose_resnet.py:155-193, deconv_layers; autograd's backward of :203):
+ *   dx[n,iy,ix,ci] = sum_{co,ky,kx} dy[n, 2iy-1+ky, 2ix-1+kx, co] * w[ci][co][ky][kx]
+ * dy: NHWC [n, 2hin, 2win, cout_pitch], dx: NHWC [n, hin, win, cin_pitch] (channels 0..cin of every pixel are written,
+ * nothing is accumulated), w_dgrad: the [16][ceil32(cin)][ceil16(cout)] operand of udp_pack_conv_weights(ks = 4).
+ * cin % 16 == 0, cin <= 2048, cout % 8 == 0, pitches % 4 == 0.  One MFMA launch over an LDS-staged halo tile of dy: no
+ * atomics, no zero-stuffed copy; a pixel's sum has one fixed order whatever the tiling. */
+int udp_deconv4s2_dgrad(const void* dy, const void* w_dgrad, int n, int hin, int win, int cin, int cin_pitch,
+                        int cout, int cout_pitch, int dtype, void* dx, void* stream);
+/* MaxPool2d(kernel 3, stride 2, padding 1) (pose_resnet.py:116, :199) on NHWC [n,h,w,c], c % 4 == 0:
+ * y [n, (h-1)/2+1, (w-1)/2+1, c].  The backward recomputes every window's arg-max -- its first maximum in row-major
+ * window order, torch.max_pool2d's rule -- and gathers: dx [n,h,w,c] is written everywhere, no index tensor, no
+ * atomics, a fixed order of the at most four addends. */
+int udp_maxpool3s2_fwd(const void* x, int n, int h, int w, int c, int dtype, void* y, void* stream);
+int udp_maxpool3s2_bwd(const void* x, const void* dy, int n, int h, int w, int c, int dtype, void* dx, void* stream);
+/* conv1 of pose_resnet.py:112 in train mode (3 -> 64, 7x7, stride 2, padding 3, no bias, no ReLU; bn1 follows
+ * unfolded, :113): x = the NHWC [n,h,w,cin_k] image of udp_nchw_to_nhwc (channels 3.. are not read), w_fwd = the
+ * [49][64][cin_k] operand of udp_pack_conv_weights(cout 64, cin 3, ks 7) -- so cin_k must be 16 --,
+ * y: NHWC [n, (h-1)/2+1, (w-1)/2+1, 64]. */
+int udp_stem7_train_fwd(const void* x, const void* w_fwd, int n, int h, int w, int cin_k, int cout, int dtype,
+                        void* y, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Training of the polarized self-attention block of pose_hrnet_psa.  Replaces

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Config 3 (training step, function.py:38-77) timing on one GPU: W32 256x192, batch 32, Adam.
-Prints ms/step and images/s; `--prof` wraps nothing -- run under rocprofv3 --kernel-trace --stats."""
+Prints ms/step and images/s; `--prof` wraps nothing -- run under rocprofv3 --kernel-trace --stats.
+
+`--model pose_resnet`: res50 256x192 (the reference's second recipe, experiments/coco/resnet/res50_256x192_d256x3_adam_lr1e-3.yaml),
+batch 32, fp32, graphed steps: ms per step, then -- from a `rocprofv3 --kernel-trace --stats` run of this script that it
+starts itself -- the share of the step the deconv head's forward, input-gradient and weight-gradient launches take, and the
+three launches timed alone (hipEvents) on the three head shapes."""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,10 +20,14 @@ ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--dtype", default="f32")
 ap.add_argument("--target", default="gaussian")
 ap.add_argument("--backend", default="nccl")
-ap.add_argument("--model", default="pose_hrnet", choices=("pose_hrnet", "pose_hrnet_psa"),
+ap.add_argument("--model", default="pose_hrnet", choices=("pose_hrnet", "pose_hrnet_psa", "pose_resnet"),
                 help="pose_hrnet_psa: a polarized self-attention block in every BasicBlock (the reference's PSA YAMLs)")
 ap.add_argument("--no-graph", action="store_true", help="one ctypes launch per kernel instead of replaying the captured step")
+ap.add_argument("--no-profile", action="store_true", help="pose_resnet: skip the rocprofv3 child run and the per-launch timing")
 a = ap.parse_args()
+if a.model == "pose_resnet":
+    from bench_train_resnet import main as resnet_main
+    sys.exit(resnet_main(a))
 # one process per GPU under torch.distributed.run (backend nccl = RCCL); plain `python` = one GPU
 world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
 if world > 1:

@@ -158,6 +158,11 @@ _SIGS = {
                                 C.c_float, _P]),
     "udp_adam_coefficients": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_int, _P]),
     "udp_adam_step_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, _P, C.c_float, _P]),
+    # training of pose_resnet: deconv input gradient, max-pool, the 7x7 stem on unfolded weights (csrc/resnet_train.hip)
+    "udp_deconv4s2_dgrad": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P]),
+    "udp_maxpool3s2_fwd": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P]),
+    "udp_maxpool3s2_bwd": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P]),
+    "udp_stem7_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
     # training of the polarized self-attention block (pose_hrnet_psa)
     "udp_psa_train_save_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "udp_psa_train_fwd_pool": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),

@@ -61,10 +61,40 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, int cout, int c
   }
 }
 
+// ConvTranspose2d(4, 2, 1) weight [cin][cout][4][4] fp32 (pose_resnet.py:155-193) ->
+//   fwd   [pt][cout_pad][cin], pt = 4*(2a+b) + 2t+u holding w[ci][co][3-a-2t][3-b-2u]   (deconv.hip, wfmt 0)
+//   dgrad [ky*4+kx][cin_pad][cout_k]                                                     (deconv_dgrad_kernel)
+template <typename T>
+__device__ __forceinline__ void pack_deconv_body(const float* __restrict__ w, int cout, int cin, T* __restrict__ fwd,
+                                                 T* __restrict__ dg) {
+  const int cout_pad = (cout + 31) / 32 * 32, cin_pad = (cin + 31) / 32 * 32, cout_k = (cout + 15) / 16 * 16;
+  const long nf = 16L * cout_pad * cin;
+  const long nd = dg ? 16L * cin_pad * cout_k : 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nf + nd; i += (long)gridDim.x * blockDim.x) {
+    if (i < nf) {
+      const int ci = i % cin, co = (i / cin) % cout_pad, pt = i / ((long)cin * cout_pad);
+      const int a = pt >> 3, b = (pt >> 2) & 1, t = (pt >> 1) & 1, u = pt & 1;
+      fwd[i] = fromf<T>(co < cout ? w[((long)ci * cout + co) * 16 + (3 - a - 2 * t) * 4 + (3 - b - 2 * u)] : 0.f);
+    } else {
+      const long k = i - nf;
+      const int co = k % cout_k, ci = (k / cout_k) % cin_pad, tp = k / ((long)cout_k * cin_pad);
+      dg[k] = fromf<T>((co < cout && ci < cin) ? w[((long)ci * cout + co) * 16 + tp] : 0.f);
+    }
+  }
+}
+template <typename T>
+__global__ void pack_deconv_kernel(const float* __restrict__ w, int cout, int cin, T* __restrict__ fwd, T* __restrict__ dg) {
+  pack_deconv_body<T>(w, cout, cin, fwd, dg);
+}
+
 // all layers of a model in one launch: blockIdx.y = layer (descriptor table in device memory)
 template <typename T>
 __global__ void pack_weights_batch_kernel(const udp_pack_desc* __restrict__ descs) {
   const udp_pack_desc d = descs[blockIdx.y];
+  if (d.reserved == 1) {       // a transposed conv: w is [cin][cout][4][4]
+    pack_deconv_body<T>(d.w, d.cout, d.cin, reinterpret_cast<T*>(d.w_fwd), reinterpret_cast<T*>(d.w_dgrad));
+    return;
+  }
   const int taps = d.ks * d.ks, cout = d.cout, cin = d.cin;
   const int cout_pad = (cout + 31) / 32 * 32, cin_k = (cin + 15) / 16 * 16, cin_pad = (cin + 31) / 32 * 32, cout_k = (cout + 15) / 16 * 16;
   const float* w = d.w;
@@ -100,6 +130,8 @@ __global__ void zero_stuff2_kernel(const T* __restrict__ in, long total_out, int
 
 // ---------------------------------------------------------------------------------------------
 // weight gradient.  dW[co][ci][ky][kx] = sum_{n,y,x} dy[n,y,x,co] * x[n, y*s+ky-pad, x*s+kx-pad, ci]
+// (ks, pad) = (1, 0), (3, 1), (7, 3) and (4, 1): the last is ConvTranspose2d(4, 2, 1) with the roles swapped -- `x` is
+// the gradient of its output, `dy` its input, and [co][ci][4][4] is the module's own weight layout.
 // Workgroup = 32 co x 32 ci x all taps over `upw` pixel units; unit = TH x TW output pixels of one
 // image staged in LDS with the matching input patch.  MFMA 16x16x4 fp32: A[m=co][k=pixel],
 // B[k=pixel][n=ci]; wave w owns the 16x16 tile (w&1, w>>1) for every tap.
@@ -120,7 +152,7 @@ constexpr int kWgPitch = 36;   // floats per staged pixel (32 channels + 4: 16-b
 template <typename T, int KS>
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   extern __shared__ float lds[];
-  constexpr int TAPS = KS * KS, PAD = KS / 2;
+  constexpr int TAPS = KS * KS, PAD = KS == 4 ? 1 : KS / 2;
   const int PX = p.TH * p.TW, PXP = (PX + 3) & ~3;
   float* sDy = lds;                       // [PXP][pitch]
   float* sX = lds + PXP * kWgPitch;       // [XH*XW][pitch]
@@ -781,9 +813,16 @@ using namespace udp;
 extern "C" int udp_pack_conv_weights(const float* w, int cout, int cin, int ks, int dtype, void* w_fwd, void* w_dgrad,
                                      void* stream) {
   if (!w || !w_fwd) return fail(UDP_ERR_ARG, "udp_pack_conv_weights: null pointer");
-  if (cout <= 0 || cin <= 0 || (ks != 1 && ks != 3)) return fail(UDP_ERR_ARG, "udp_pack_conv_weights: shape");
+  if (cout <= 0 || cin <= 0 || (ks != 1 && ks != 3 && ks != 4 && ks != 7)) return fail(UDP_ERR_ARG, "udp_pack_conv_weights: shape");
   if (check_dtype(dtype, "udp_pack_conv_weights")) return UDP_ERR_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (ks == 4) {       // ConvTranspose2d(4, 2, 1): w is [cin][cout][4][4]
+    if (dtype != UDP_F32) return fail(UDP_ERR_UNSUPPORTED, "udp_pack_conv_weights: the transposed conv is fp32 only");
+    if (cin % 16) return fail(UDP_ERR_ARG, "udp_pack_conv_weights: transposed conv: cin %d is not a multiple of 16", cin);
+    const long tot = 16L * ((long)rup(cout, 32) * cin + (w_dgrad ? (long)rup(cin, 32) * rup(cout, 16) : 0));
+    pack_deconv_kernel<float><<<nblocks(tot, 256, 4096), 256, 0, s>>>(w, cout, cin, (float*)w_fwd, (float*)w_dgrad);
+    return launched("udp_pack_conv_weights");
+  }
   const int cout_pad = rup(cout, 32), cin_k = rup(cin, 16), cin_pad = rup(cin, 32), cout_k = rup(cout, 16);
   const long total = (long)ks * ks * ((long)cout_pad * cin_k + (w_dgrad ? (long)cin_pad * cout_k : 0));
   UDP_DISPATCH_T(dtype,
@@ -836,10 +875,14 @@ struct WgradPlan {
 static int wgrad_plan(int n, int hin, int win, int cin_k, int hout, int wout, int cout_k, int ks, int stride, int cout,
                       int cin, int dtype, size_t workspace_bytes, WgradPlan* g) {
   if (check_dtype(dtype, "udp_conv2d_wgrad")) return UDP_ERR_ARG;
-  if (n <= 0 || (ks != 1 && ks != 3) || (stride != 1 && stride != 2) || cout <= 0 || cin <= 0 || cout > cout_k ||
-      cin > cin_k || (cin_k & 3) || (cout_k & 3))
+  if (n <= 0 || (ks != 1 && ks != 3 && ks != 4 && ks != 7) || (stride != 1 && stride != 2) || cout <= 0 || cin <= 0 ||
+      cout > cout_k || cin > cin_k || (cin_k & 3) || (cout_k & 3))
     return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: shape");
-  const int pad = ks / 2;
+  if (ks == 4 && (stride != 2 || hin != 2 * hout || win != 2 * wout))
+    return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: ks 4 is the transposed conv (4, 2, 1): stride 2 and x twice the size of dy");
+  if ((ks == 4 || ks == 7) && dtype != UDP_F32)
+    return fail(UDP_ERR_UNSUPPORTED, "udp_conv2d_wgrad: ks %d is fp32 only", ks);
+  const int pad = ks == 4 ? 1 : ks / 2;
   if (hout != (hin + 2 * pad - ks) / stride + 1 || wout != (win + 2 * pad - ks) / stride + 1)
     return fail(UDP_ERR_ARG, "udp_conv2d_wgrad: output size does not match input/stride");
   const bool bf = dtype == UDP_BF16 && getenv("UDP_POSE_WGRAD_F32MFMA") == nullptr;
@@ -920,7 +963,10 @@ static int wgrad_partials(const void* x, const void* dy, int n, int hin, int win
   const dim3 grid(g.tiles, g.splits);
   const void* fn;
   if (g.family == 0)
-    fn = ks == 3 ? reinterpret_cast<const void*>(&wgrad_kernel<float, 3>) : reinterpret_cast<const void*>(&wgrad_kernel<float, 1>);
+    fn = ks == 7   ? reinterpret_cast<const void*>(&wgrad_kernel<float, 7>)
+         : ks == 4 ? reinterpret_cast<const void*>(&wgrad_kernel<float, 4>)
+         : ks == 3 ? reinterpret_cast<const void*>(&wgrad_kernel<float, 3>)
+                   : reinterpret_cast<const void*>(&wgrad_kernel<float, 1>);
   else if (g.family == 1)
     fn = ks == 3 ? reinterpret_cast<const void*>(&wgrad_bf16_kernel<3>) : reinterpret_cast<const void*>(&wgrad_bf16_kernel<1>);
   else

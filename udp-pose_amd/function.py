@@ -4,7 +4,7 @@
 * ``JointsMSELoss`` / ``JointsMSELoss_offset`` (loss.py:15-39 / :41-76): callables returning the loss
   value(s) as device fp64 scalars (``udp_mse_loss``); ``.last_grad`` holds d loss / d output.
 * ``train(config, train_loader, model, criterion, optimizer, epoch, ...)``: ``model`` is what
-  ``MODELS[name](cfg, is_train=True)`` returned; its ``train.HRNetTrainer`` owns parameters, Adam moments and the
+  ``MODELS[name](cfg, is_train=True)`` returned; its trainer (a ``train.Trainer``: HRNet or pose_resnet) owns parameters, Adam moments and the
   backward.  ``criterion`` and ``optimizer`` are honoured (use_target_weight; lr / betas / eps per batch) and
   anything the kernels do not implement (another loss, SGD, weight decay) raises instead of being ignored.
 * ``validate(config, val_loader, val_dataset, model, criterion, ...)``: forward + mirrored forward in one
@@ -155,12 +155,12 @@ def _check_criterion(criterion, target_type):
 def train(config, train_loader, model, criterion, optimizer, epoch=0, output_dir=None, tb_log_dir=None,
           writer_dict=None, world_size=1):
     """function.py:27-111: ``model.train()``, then per batch forward -> criterion -> backward -> optimizer step.
-    ``model`` is what ``MODELS[name](cfg, is_train=True)`` returned (or a train.HRNetTrainer); ``criterion`` must be
+    ``model`` is what ``MODELS[name](cfg, is_train=True)`` returned (or any train.Trainer); ``criterion`` must be
     JointsMSELoss / JointsMSELoss_offset and ``optimizer`` Adam over ``model.parameters()`` -- their
     hyper-parameters (use_target_weight; lr, betas, eps, re-read every batch) are honoured, anything else raises.
     Returns the sample-weighted mean loss of the epoch (what ``losses.avg`` holds)."""
-    from .train import HRNetTrainer
-    if isinstance(model, HRNetTrainer):
+    from .train import Trainer
+    if isinstance(model, Trainer):
         trainer = model
     else:
         model.train()
@@ -179,7 +179,7 @@ def train(config, train_loader, model, criterion, optimizer, epoch=0, output_dir
             loss = trainer.train_step_graphed(x, tg, tw, world_size=world_size)
         else:
             loss = trainer.train_step(x, tg, tw, world_size=world_size)
-        if not isinstance(model, HRNetTrainer):
+        if not isinstance(model, Trainer):
             model._stale = True
         total += loss * n
         count += n

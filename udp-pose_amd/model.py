@@ -69,7 +69,7 @@ class PoseNetHip:
         return dict(self._sd or {})
 
     def trainer(self):
-        raise NotImplementedError("%s: the training step covers pose_hrnet only" % self.NAME)
+        raise NotImplementedError("%s: the training step covers pose_hrnet, pose_hrnet_psa and pose_resnet only" % self.NAME)
 
     def to(self, device):
         self.device = torch.device(device)
@@ -207,7 +207,58 @@ class PoseNetHip:
     forward = __call__
 
 
-class PoseHighResolutionNetHip(PoseNetHip):
+class _Trainable:
+    """The training surface function.train drives (tools/train.py:91,116-125), shared by the nets that have a trainer:
+    ``trainer()`` (created on first use from the current state_dict by ``_make_trainer``), ``parameters()``, and the
+    staleness handling that re-reads the weights from the trainer once it has stepped."""
+
+    _trainer = None              # the train.Trainer over the same weights (created by .train())
+    _stale = False               # legacy flag (function.train sets it); the trainer's version counter decides
+    _seen_version = 0            # trainer.version the inference program / state_dict were last synced at
+
+    def _make_trainer(self):
+        raise NotImplementedError
+
+    def trainer(self):
+        """The trainer over this model's weights (created on first use from the current state_dict)."""
+        if self._trainer is None:
+            if self._sd is None:
+                raise RuntimeError("load_state_dict() or init_weights() first")
+            if self.device is None:
+                self.to("cuda")
+            self._trainer = self._make_trainer()
+        return self._trainer
+
+    def parameters(self):
+        """What ``optim.Adam(model.parameters(), lr=...)`` (utils.py:70-74) takes: ONE flat fp32 device tensor
+        holding every parameter in named_parameters() order (the trainer's master copy)."""
+        t = self.trainer()
+        return [t.flat[:t._n_param]]
+
+    def _trainer_moved(self):
+        """True when the trainer has stepped (by whatever route: function.train, train_step, adam_step) since the
+        compiled inference program and ``_sd`` were last read from it."""
+        return self._trainer is not None and (self._stale or self._trainer.version != self._seen_version)
+
+    def _sync_from_trainer(self):
+        self._sd = self._trainer.state_dict()
+        self._stale = False
+        self._seen_version = self._trainer.version
+        self._release()
+
+    def _refresh(self):
+        if self._trainer_moved():
+            self._sync_from_trainer()                      # weights moved since the program was compiled
+
+    def _set_weights(self, sd):
+        """Fresh weights (init_weights): any trainer over the old ones is dropped."""
+        self._sd = sd
+        self._trainer, self._seen_version, self._stale = None, 0, False
+        self._release()
+        return self
+
+
+class PoseHighResolutionNetHip(_Trainable, PoseNetHip):
     """HRNet (UDP variant) on MI355X through the C ABI: inference, plus the training surface function.train drives."""
 
     NAME = "pose_hrnet"
@@ -216,9 +267,6 @@ class PoseHighResolutionNetHip(PoseNetHip):
     def __init__(self, cfg, dtype="f32", psa=False):
         super().__init__(cfg, dtype)
         self.psa = bool(psa)
-        self._trainer = None         # train.HRNetTrainer over the same weights (created by .train())
-        self._stale = False          # legacy flag (function.train sets it); the trainer's version counter decides
-        self._seen_version = 0       # trainer.version the inference program / state_dict were last synced at
         self.extra = _get(cfg, "MODEL", "EXTRA")
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
@@ -267,44 +315,11 @@ class PoseHighResolutionNetHip(PoseNetHip):
                     sd[name] = v
         elif pretrained:
             raise ValueError("%s is not exist!" % pretrained)       # pose_hrnet.py:503-505
-        self._sd = sd
-        self._trainer, self._seen_version = None, 0
-        self._release()
-        return self
+        return self._set_weights(sd)
 
-    # ---- training surface (function.train drives it; tools/train.py:91,116-125)
-    def trainer(self):
-        """The HRNetTrainer over this model's weights (created on first use from the current state_dict)."""
-        if self._trainer is None:
-            if self._sd is None:
-                raise RuntimeError("load_state_dict() or init_weights() first")
-            from .train import HRNetTrainer
-            if self.device is None:
-                self.to("cuda")
-            self._trainer = HRNetTrainer(self.cfg, self._sd, device=self.device, dtype="bf16" if self.dtype == "bf16" else "f32",
-                                         psa=self.psa)
-        return self._trainer
-
-    def parameters(self):
-        """What ``optim.Adam(model.parameters(), lr=...)`` (utils.py:70-74) takes: ONE flat fp32 device tensor
-        holding every parameter in named_parameters() order (the trainer's master copy)."""
-        t = self.trainer()
-        return [t.flat[:t._n_param]]
-
-    def _trainer_moved(self):
-        """True when the trainer has stepped (by whatever route: function.train, train_step, adam_step) since the
-        compiled inference program and ``_sd`` were last read from it."""
-        return self._trainer is not None and (self._stale or self._trainer.version != self._seen_version)
-
-    def _sync_from_trainer(self):
-        self._sd = self._trainer.state_dict()
-        self._stale = False
-        self._seen_version = self._trainer.version
-        self._release()
-
-    def _refresh(self):
-        if self._trainer_moved():
-            self._sync_from_trainer()                      # weights moved since the program was compiled
+    def _make_trainer(self):
+        from .train import HRNetTrainer
+        return HRNetTrainer(self.cfg, self._sd, device=self.device, dtype="bf16" if self.dtype == "bf16" else "f32", psa=self.psa)
 
 
 class RSN18Hip(PoseNetHip):
@@ -386,21 +401,26 @@ def get_pose_net_psa(cfg, is_train, **kwargs):
     return get_pose_net(cfg, is_train, psa=True, **kwargs)
 
 
-class PoseResNetHip(PoseNetHip):
+class PoseResNetHip(_Trainable, PoseNetHip):
     """pose_resnet / SimpleBaseline (deep_hrnet/lib/models/pose_resnet.py:105-273: ResNet-50 / 101 / 152, three
-    ConvTranspose2d(4, 2, 1) + BN + ReLU, ``final_layer``) inference through the same C ABI; ``state_dict`` in the
-    reference module's key format.  Storage modes "f32" and "f16x2" (the deconv kernel has no bf16 form)."""
+    ConvTranspose2d(4, 2, 1) + BN + ReLU, ``final_layer``) through the same C ABI; ``state_dict`` in the reference
+    module's key format.  Storage modes "f32" and "f16x2" (the deconv kernel has no bf16 form).  ``trainable`` (what
+    ``MODELS["pose_resnet"](cfg, is_train=True)`` sets): the model also has the training surface of
+    ``PoseHighResolutionNetHip`` -- ``init_weights``, ``train()``, ``parameters()``, ``trainer()`` (a
+    train.PoseResNetTrainer, fp32 whatever the storage mode of the inference program)."""
 
     NAME = "pose_resnet"
     DTYPES = ("f32", "f16x2")
+    TRAINS = True                # a net of this class can be built trainable
 
-    def __init__(self, cfg, dtype="f32"):
+    def __init__(self, cfg, dtype="f32", trainable=False):
         if dtype not in self.DTYPES:
             raise ValueError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
         super().__init__(cfg, dtype)
         self.extra = _get(cfg, "MODEL", "EXTRA")
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.spec = self._spec_of(self.extra)             # NotImplementedError for depths / kernels without a kernel
+        self.trainable = bool(trainable) and self.TRAINS
 
     @staticmethod
     def _spec_of(extra):
@@ -415,7 +435,49 @@ class PoseResNetHip(PoseNetHip):
                                         deconv_with_bias=sp["deconv_with_bias"])
 
     def init_weights(self, pretrained=""):
-        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+        """pose_resnet.py:211-251.  With a pretrained file: the deconv and final convs ~ N(0, 0.001), their biases 0, the
+        deconv BatchNorms 1 / 0, then a non-strict load of the file (the ImageNet backbone; what it lacks keeps the
+        values above, and what the file does not cover of the backbone the nn.Module defaults reduced to BatchNorm 1 / 0,
+        convs ~ N(0, 0.001)).  Without one: every conv and deconv ~ N(0, 0.001), every BatchNorm 1 / 0.  Draws come from
+        torch's global generator like nn.init.normal_ (module iteration order is not reproduced)."""
+        import os
+        if not self.trainable:
+            raise NotImplementedError("%s: built with is_train=False (inference only); load a state_dict" % self.NAME)
+        shapes = self.param_shapes()
+        sd = {}
+        for k, shape in shapes.items():
+            if k.endswith("num_batches_tracked"):
+                sd[k] = torch.zeros((), dtype=torch.int64)
+            elif k.endswith("running_var"):
+                sd[k] = torch.ones(shape)
+            elif k.endswith("running_mean"):
+                sd[k] = torch.zeros(shape)
+            elif len(shape) == 4:
+                sd[k] = torch.randn(shape) * 0.001            # Conv2d / ConvTranspose2d
+            elif k.endswith(".weight") and (k[:-7] + ".running_mean") in shapes:
+                sd[k] = torch.ones(shape)                     # BatchNorm weight
+            else:
+                sd[k] = torch.zeros(shape)                    # BatchNorm / deconv / final conv bias
+        if pretrained and os.path.isfile(pretrained):
+            for name, v in torch.load(pretrained, map_location="cpu", weights_only=True).items():
+                name = name[7:] if name.startswith("module.") else name
+                if name not in sd:
+                    continue                                  # strict=False: the classifier of an ImageNet file
+                if tuple(v.shape) != tuple(sd[name].shape):
+                    raise RuntimeError("size mismatch for %s: %s vs %s" % (name, tuple(v.shape), tuple(sd[name].shape)))
+                sd[name] = v
+        return self._set_weights(sd)
+
+    def trainer(self):
+        if not self.trainable:
+            raise NotImplementedError("%s: built with is_train=False (inference only); MODELS[%r](cfg, is_train=True) "
+                                      "returns the trainable model" % (self.NAME, self.NAME))
+        return super().trainer()
+
+    def _make_trainer(self):
+        from .train import PoseResNetTrainer
+        return PoseResNetTrainer(self.spec, self.num_joints, _get(self.cfg, "MODEL", "TARGET_TYPE"), self._sd,
+                                 device=self.device, dtype="f32")
 
     def _make_program(self, h, w):
         from .resnet_plan import PoseResNetProgram
@@ -423,9 +485,21 @@ class PoseResNetHip(PoseNetHip):
 
 
 def get_pose_net_resnet(cfg, is_train, **kwargs):
-    """pose_resnet.py:263-273 (``get_pose_net``): the model for MODEL.EXTRA.NUM_LAYERS; inference only -- the weights
-    come from ``load_state_dict`` (training, hence ``init_weights`` under is_train, is out of scope)."""
-    return PoseResNetHip(cfg, **kwargs)
+    """pose_resnet.py:263-273 (``get_pose_net``): the model for MODEL.EXTRA.NUM_LAYERS, trainable under ``is_train``
+    (``init_weights(cfg.MODEL.PRETRAINED)`` when cfg.MODEL.INIT_WEIGHTS says so, :270-271)."""
+    model = PoseResNetHip(cfg, trainable=bool(is_train), **kwargs)
+    if is_train:
+        try:
+            init = bool(_get(cfg, "MODEL", "INIT_WEIGHTS"))
+        except (KeyError, AttributeError):
+            init = False
+        if init:
+            try:
+                pretrained = _get(cfg, "MODEL", "PRETRAINED")
+            except (KeyError, AttributeError):
+                pretrained = ""
+            model.init_weights(pretrained or "")
+    return model
 
 
 class PoseResNetPsaHip(PoseResNetHip):
@@ -435,6 +509,7 @@ class PoseResNetPsaHip(PoseResNetHip):
     The same deconv head, ``final_layer``, storage modes and refusals."""
 
     NAME = "pose_resnet_psa"
+    TRAINS = False               # inference only whatever is_train says: no backward for its BasicBlock + PSA stages
 
     @staticmethod
     def _spec_of(extra):

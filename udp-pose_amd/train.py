@@ -1,9 +1,10 @@
 """Training step on MI355X: the host side of deep_hrnet/lib/core/function.py:38-77.
 
-``HRNetTrainer`` owns the parameters (one flat fp32 buffer in ``named_parameters()`` order, so
-the gradient of the whole model is ONE contiguous bucket for the RCCL all-reduce), runs the
-train-mode forward of lib/models/pose_hrnet.py:436-471 op by op through the C ABI, keeps the tape
-and walks it backwards (``loss.backward()``), then ``udp_adam_step`` (``optimizer.step()``).
+``Trainer`` owns the parameters (one flat fp32 buffer in ``named_parameters()`` order, so
+the gradient of the whole model is ONE contiguous bucket for the RCCL all-reduce), keeps the tape
+of the train-mode forward its subclass runs op by op through the C ABI, walks it backwards
+(``loss.backward()``), then ``udp_adam_step`` (``optimizer.step()``).  ``HRNetTrainer`` is the graph of
+lib/models/pose_hrnet.py:436-471 (and pose_hrnet_psa), ``PoseResNetTrainer`` that of lib/models/pose_resnet.py:195-209.
 torch is used for device memory only; every arithmetic step is a kernel of libudp_pose_hip.so.
 
 Reference contract mirrored: ``JointsMSELoss`` / ``JointsMSELoss_offset`` (lib/core/loss.py),
@@ -61,24 +62,24 @@ class _Group:
             y.grad = v
 
 
-class HRNetTrainer:
-    def __init__(self, cfg, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, psa=False,
-                 bucket_elems=6 * 1024 * 1024):
-        """``psa``: the pose_hrnet_psa variant -- a PSA_s ("<block>.deattn.*") after relu(bn1) of every BasicBlock
-        (pose_hrnet_psa.py:37,49), trained through the udp_psa_train_* entry points.  ``bucket_elems``: gradient elements
-        per all-reduce bucket (the default is ~25 MB)."""
-        from .model import _get
-        self.psa = bool(psa)
-        self.extra = _get(cfg, "MODEL", "EXTRA")
-        self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
-        self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
+class Trainer:
+    """Everything of the training step that is not one net's graph: the flat parameter / gradient / Adam buffers, the
+    pack table, the primitive ops with their tape entries (``_conv``, ``_bn``, ``_sum_relu``), the backward walk with
+    its gradient buckets, the criterion, Adam and the captured step.  A subclass supplies ``forward`` (which fills
+    ``self._tape`` and sets ``self._out``) and may override ``_conv_entry``."""
+
+    def __init__(self, shapes, state_dict, num_joints, target_type, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-8, bucket_elems=6 * 1024 * 1024):
+        """``shapes``: the net's state_dict contract (key -> shape, registration order).  ``bucket_elems``: gradient
+        elements per all-reduce bucket (the default is ~25 MB)."""
+        self.num_joints = int(num_joints)
+        self.target_type = target_type
         self.device = torch.device(device)
         self.dtype = dtype
         self._dt = _lib.UDP_BF16 if dtype == "bf16" else _lib.UDP_F32
         self._tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
         self.lr, self.betas, self.eps = lr, betas, eps
         self.step_count = 0
-        shapes = hrnet_param_shapes(self.extra, self.num_joints, self.target_type, psa=self.psa)
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         missing = [k for k in shapes if k not in sd and not k.endswith("num_batches_tracked")]
         if missing:
@@ -100,21 +101,28 @@ class HRNetTrainer:
         self.exp_avg = torch.zeros_like(self.grad)
         self.exp_avg_sq = torch.zeros_like(self.grad)
         # packed conv operands, refreshed from the fp32 master weights every step
-        self._convs = {}
+        self._convs, self._transposed = {}, set()
         esz = 2 if dtype == "bf16" else 4
-        ws_bytes = 0
+        ws_bytes, widest = 0, 1024
         for k in self._keys:
             s = shapes[k]
             if len(s) != 4:
                 continue
-            if ".deattn." in k and not k.endswith(".conv_v_left.weight"):
-                continue            # the attention block reads its small fp32 matrices as they are; only theta is a conv
-            cout, cin, ks = s[0], s[1], s[2]
+            ent = self._conv_entry(k, s)
+            if ent is None:
+                continue
+            cout, cin, ks, transposed, needs_dgrad = ent
+            if transposed:
+                if dtype != "f32" or ks != 4 or cin % 16 or cout % 16:
+                    raise ValueError("%s: transposed convs are fp32, 4x4, with channel counts in multiples of 16" % k)
+                self._transposed.add(k[:-len(".weight")])
+            # (a transposed conv's operands have the same sizes: [16][ceil32(cout)][cin] and [16][ceil32(cin)][ceil16(cout)])
             fwd = torch.empty(ks * ks * _rup(cout, 32) * _rup(cin, 16) * esz, dtype=torch.uint8, device=self.device)
             dg = None
-            if k != "conv1.weight":
+            if needs_dgrad:
                 dg = torch.empty(ks * ks * _rup(cin, 32) * _rup(cout, 16) * esz, dtype=torch.uint8, device=self.device)
             self._convs[k[:-len(".weight")]] = (cout, cin, ks, fwd, dg)
+            widest = max(widest, _rup(cout, 32), _rup(cin, 32))
             ws_bytes = max(ws_bytes, _lib.lib().udp_conv2d_wgrad_workspace_bytes(cout, cin, ks))
         self._wgrad_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
         # one more per branch slot: the weight gradients of a lock-step level keep their partials until the common reduce
@@ -124,16 +132,15 @@ class HRNetTrainer:
             descs[i].w, descs[i].w_fwd = self._p(name + ".weight"), fwd.data_ptr()
             descs[i].w_dgrad = None if dg is None else dg.data_ptr()
             descs[i].cout, descs[i].cin, descs[i].ks = cout, cin, ks
+            descs[i].reserved = int(name in self._transposed)
         self._pack_table = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.device)
-        self._zeros = torch.zeros(1024, dtype=torch.float32, device=self.device)      # zero bias rows
+        self._zeros = torch.zeros(widest, dtype=torch.float32, device=self.device)    # zero bias rows
         # one BatchNorm workspace per branch slot: the branches of a module run in lock step (_blocks_lockstep), a
         # conv's epilogue leaves its partial rows in its slot until the multi-tensor BatchNorm call has read them
         bn_c = max([shapes[k][0] for k in self._keys if len(shapes[k]) == 1] + [64])     # widest BatchNorm of this net
         self._bn_wss = [torch.zeros(_lib.lib().udp_bn_workspace_doubles(bn_c), dtype=torch.float64, device=self.device)
                         for _ in range(4)]
         self._bn_ws = self._bn_wss[0]
-        self.bn_multi = os.environ.get("UDP_POSE_NO_BN_MULTI") is None           # A/B knob
-        self.conv_multi = os.environ.get("UDP_POSE_NO_CONV_MULTI") is None       # A/B knob (merged branch convs)
         self._loss = torch.zeros(2, dtype=torch.float64, device=self.device)
         self._graphs, self._warm, self._coef = {}, set(), None            # train_step_graphed
         self.version = 0                      # bumped by every optimizer step (the owning model's staleness check)
@@ -158,6 +165,14 @@ class HRNetTrainer:
             if end - lo >= self.bucket_elems or i + 1 == len(self._keys):
                 self._buckets.append((lo, end, cnt))
                 lo, cnt = end, 0
+
+    def _conv_entry(self, key, shape):
+        """(cout, cin, ks, transposed, needs an input gradient) of the 4-d parameter ``key`` for the pack table, or
+        None when no conv kernel reads it.  A transposed conv's weight is [cin][cout][4][4]."""
+        return shape[0], shape[1], shape[2], False, key != "conv1.weight"
+
+    def forward(self, x):
+        raise NotImplementedError
 
     # ------------------------------------------------------------------ parameter views
     def _p(self, key):
@@ -337,6 +352,282 @@ class HRNetTrainer:
                                                    0, 0, 0, self._dt, self._stream()))
         self._tape.append((y, backward, save, [name + ".weight", name + ".bias"]))
         return y
+
+    def _sum_relu(self, terms):
+        """y = relu(sum_k up(term_k, shift_k)): HighResolutionModule.forward :266-272."""
+        L = _lib.lib()
+        t0 = terms[0][0]
+        y = self._new(t0.n, t0.h << terms[0][1], t0.w << terms[0][1], t0.c)
+        # ONE launch: y = relu(((t0 + t1) + t2) + ...), the terms added in the reference's order (udp_conv2d_fused, UDP_OP_FUSE:
+        # in + res + up to three addends, each up-sampled by its shift; shift 0 = same resolution); fp32 tensors: the numbers of
+        # the term-by-term launches below, bit for bit
+        second = len(terms) > 1 and terms[1][1] == 0           # `res` carries no shift
+        rest = terms[2:] if second else terms[1:]
+        if self.fuse_sums and terms[0][1] == 0 and len(rest) <= 3:
+            op = self._conv_op(1, 1, y.ck, y.ck, y.h, y.w, y.h, y.w)
+            op.kind, op.relu, op.n_up = _lib.UDP_OP_FUSE, 1, len(rest)
+            for k, (t, s) in enumerate(rest):
+                op.up_shift[k] = s
+            up_ptrs = [t.buf.data_ptr() for t, _ in rest] + [None] * (3 - len(rest))
+            _lib.check(L.udp_conv2d_fused(C.byref(op), self._dt, y.n, terms[0][0].buf.data_ptr(), None, None,
+                                          terms[1][0].buf.data_ptr() if second else None, up_ptrs[0], up_ptrs[1], up_ptrs[2],
+                                          y.buf.data_ptr(), self._stream()))
+        else:
+            for k, (t, s) in enumerate(terms):
+                _lib.check(L.udp_ew_accumulate(y.buf.data_ptr(), t.buf.data_ptr(), y.n, y.h, y.w, y.ck, s, int(k == 0),
+                                               int(k == len(terms) - 1), self._dt, self._stream()))
+
+        def backward():
+            g = self._like(y)
+            _lib.check(L.udp_relu_bwd(y.grad.data_ptr(), y.buf.data_ptr(), g.data_ptr(), g.numel(), self._dt,
+                                      self._stream()))
+            handed = not self.fuse_sums
+            for t, s in terms:
+                if not t.needs_grad:
+                    continue
+                have = t.grad is not None
+                if s == 0 and not have and not handed:
+                    # the first same-resolution term without a gradient yet takes g itself instead of a copy of it: every
+                    # other term of this sum reads g inside this function, later writers of t.grad come later on the tape
+                    t.grad = g
+                    handed = True
+                    continue
+                if not have:
+                    t.grad = self._like(t)
+                if s == 0:
+                    _lib.check(L.udp_ew_accumulate(t.grad.data_ptr(), g.data_ptr(), t.n, t.h, t.w, t.ck, 0, int(not have),
+                                                   0, self._dt, self._stream()))
+                else:
+                    _lib.check(L.udp_upsample_bwd(g.data_ptr(), y.n, y.h, y.w, y.ck, s, t.grad.data_ptr(), int(have),
+                                                  self._dt, self._stream()))
+        self._tape.append((y, backward, None, []))
+        return y
+
+    def _backward_walk(self, dheat, pre=None):
+        """The tape in reverse.  Yields the list of gradient buckets a backward node has just completed (the node wrote
+        their last gradient), and finally the buckets no node completed (a bucket with an unused parameter: its gradient
+        stays as is).  ``pre()`` is called before anything is launched after a yield (segmented graph capture opens its
+        next segment there).  Every parameter gradient is overwritten (implicit zero_grad)."""
+        L = _lib.lib()
+        if pre:
+            pre()
+        o = self._out
+        g = torch.empty(o.n * o.h * o.w * o.ck, dtype=self._tdt, device=self.device)
+        _lib.check(L.udp_nchw_to_nhwc(dheat.data_ptr(), o.n, o.c, o.h, o.w, o.ck, g.data_ptr(), self._dt, self._stream()))
+        o.grad = g
+        left = [c for _, _, c in self._buckets]
+        for y, bwd, _, keys in reversed(self._tape):
+            done = []
+            if y.grad is not None:
+                if pre:
+                    pre()
+                bwd()
+                for k in keys:
+                    b = self._bucket_of[k]
+                    left[b] -= 1
+                    if left[b] == 0:
+                        done.append(b)
+            y.grad = None
+            if done:
+                self._join_side()             # the bucket's weight gradients were written on the side stream
+                yield done
+        self._tape = []
+        self._join_side()
+        rest = [b for b, n_left in enumerate(left) if n_left > 0]
+        if rest:
+            yield rest
+
+    def backward(self, dheat, world_size=1):
+        """dheat: fp32 [N,C,h,w] = d loss / d heat-maps.  Fills self.grad (zero_grad is implicit: every
+        parameter gradient is overwritten).  ``world_size > 1``: every gradient bucket is SUM-all-reduced
+        (asynchronously, on the communication stream of torch.distributed) as soon as its last gradient has been
+        written, overlapping the rest of the backward; on return all buckets are reduced."""
+        works = []
+        self.reduce_order = []                # bucket indices in the order their all-reduce was issued
+        for done in self._backward_walk(dheat):
+            if world_size > 1:
+                works += [self._reduce_bucket(b) for b in done]
+        for w in works:
+            w.wait()
+
+    def _reduce_bucket(self, b):
+        from .dist import allreduce_sum_async
+        lo, hi, _ = self._buckets[b]
+        self.reduce_order.append(b)
+        if os.environ.get("UDP_POSE_FAKE_ALLREDUCE"):        # timing diagnosis only (tools/bench_train.py): no exchange
+            class _Done:
+                def wait(self):
+                    return True
+            return _Done()
+        return allreduce_sum_async(self.grad[lo:hi])
+
+    def loss_and_grad(self, heat, target, target_weight):
+        """criterion(output, target, target_weight) (loss.py:15-76) and its gradient w.r.t. output."""
+        b, c = heat.shape[:2]
+        off = self.target_type == "offset"
+        j = c // 3 if off else c
+        d = torch.empty_like(heat)
+        _lib.check(_lib.lib().udp_mse_loss(heat.data_ptr(), target.data_ptr(), target_weight.data_ptr(), b, j,
+                                           heat.shape[2] * heat.shape[3], int(off), self._loss.data_ptr(), d.data_ptr(),
+                                           self._stream()))
+        self._loss_grad = d
+        return self._loss, d
+
+    def adam_step(self, grad_scale=1.0):
+        """optimizer.step(): torch.optim.Adam(lr) on the flat parameter buffer (utils.py:70-74).
+        ``grad_scale``: 1/world_size after the SUM all-reduce of the gradient."""
+        self.step_count += 1
+        self.version += 1                                   # owners compare it with the version they last read
+        _lib.check(_lib.lib().udp_adam_step(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
+                                            self.exp_avg_sq.data_ptr(), self._n_param, self.lr, self.betas[0],
+                                            self.betas[1], self.eps, self.step_count, float(grad_scale),
+                                            self._stream()))
+
+    def _adam_step_dev(self, grad_scale=1.0):
+        _lib.check(_lib.lib().udp_adam_step_dev(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
+                                                self.exp_avg_sq.data_ptr(), self._n_param, self.betas[0], self.betas[1],
+                                                self.eps, self._coef.data_ptr(), float(grad_scale), self._stream()))
+
+    def train_step_graphed(self, x, target, target_weight, world_size=1):
+        """train_step with the whole step (weight packing, forward, criterion, backward, Adam: ~1900
+        launches issued from the Python tape) captured ONCE per input shape as a hipGraph (torch.cuda.graph: stream
+        capture of our launches on torch's capture stream, activations from the graph's private pool) and replayed:
+        the host then costs one graph launch per step instead of one ctypes call per kernel.  The first step of a
+        shape runs eagerly (lazy one-time initialisation must not be captured), the second captures and replays.
+        Arithmetic and results are those of train_step, bit for bit; the learning rate may change between steps
+        (it only enters through Adam's two scalars, uploaded before every replay), betas / eps are part of the key.
+        At most two shapes stay captured (a full and a ragged last batch).
+
+        ``world_size > 1`` (one process per GPU, config 3): the step is captured in SEGMENTS that end where a gradient
+        bucket receives its last gradient -- forward + criterion + the backward of the last layers; the backward
+        between two bucket boundaries; ...; and Adam on its own.  A replayed step is: replay segment 0, issue the
+        asynchronous SUM all-reduce of its bucket(s) from the host (torch.distributed orders it behind the segment on
+        its communication stream: RCCL over xGMI, or gloo), replay segment 1 at once -- the exchange runs under it, as
+        DistributedDataParallel's reducer overlaps the reference's backward -- and so on; the work handles are waited
+        for (stream order, no host block under RCCL) before the Adam graph with grad_scale 1 / world_size.  All
+        segments share one memory pool and are always replayed in capture order.  Same arithmetic, same bucket order
+        and the same results as train_step(world_size), bit for bit."""
+        key = (tuple(x.shape), tuple(target.shape), tuple(target_weight.shape), self.betas, self.eps, int(world_size))
+        ent = self._graphs.get(key)
+        if ent is None:
+            if key not in self._warm:                                # first step of this shape: eager
+                self._warm.add(key)
+                return self.train_step(x, target, target_weight, world_size=world_size)
+            if self._coef is None:
+                self._coef = torch.zeros(2, dtype=torch.float32, device=self.device)
+                # pinned staging slots for the asynchronous upload of Adam's two scalars: the host runs steps ahead
+                # of the GPU, a slot is rewritten only after the copy that read it has completed (its event)
+                self._coef_host = [torch.zeros(2, dtype=torch.float32).pin_memory() for _ in range(4)]
+                self._coef_done = [None] * 4
+            gx, gt, gw = x.clone(), target.contiguous().clone(), target_weight.contiguous().clone()
+            torch.cuda.synchronize()             # the last replay of an evicted graph may still be running
+            while len(self._graphs) >= 2:
+                self._graphs.pop(next(iter(self._graphs)))
+            if world_size == 1:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    heat = self.forward(gx)
+                    self.loss_and_grad(heat, gt, gw)
+                    self.backward(self._loss_grad)
+                    self._adam_step_dev()
+                segs = [(graph, [])]
+            else:
+                segs = self._capture_segments(gx, gt, gw, 1.0 / world_size)
+            ent = self._graphs[key] = (segs, gx, gt, gw)
+        segs, gx, gt, gw = ent
+        gx.copy_(x, non_blocking=True)
+        gt.copy_(target, non_blocking=True)
+        gw.copy_(target_weight, non_blocking=True)
+        self.step_count += 1
+        slot = self.step_count % 4
+        if self._coef_done[slot] is not None:
+            self._coef_done[slot].synchronize()
+        _lib.check(_lib.lib().udp_adam_coefficients(self.lr, self.betas[0], self.betas[1], self.step_count,
+                                                    self._coef_host[slot].data_ptr()))
+        self._coef.copy_(self._coef_host[slot], non_blocking=True)
+        self._coef_done[slot] = torch.cuda.Event()
+        self._coef_done[slot].record()
+        works = []
+        self.reduce_order = []
+        for graph, buckets in segs:
+            if graph is None:                                        # every bucket is reduced: Adam may read the gradient
+                for w in works:
+                    w.wait()
+                continue
+            graph.replay()
+            works += [self._reduce_bucket(b) for b in buckets]
+        self.version += 1
+        return self._loss
+
+    def _capture_segments(self, gx, gt, gw, grad_scale):
+        """The step as a list of (graph, buckets to all-reduce after it) in replay order, a (None, []) marker where
+        the outstanding all-reduces must be waited for, and the Adam graph last."""
+        pool = torch.cuda.graph_pool_handle()
+        segs = []
+        cur = []                                    # [graph, context] of the segment being captured, or empty
+
+        def begin():
+            if not cur:
+                g = torch.cuda.CUDAGraph()
+                ctx = torch.cuda.graph(g, pool=pool)
+                ctx.__enter__()
+                cur[:] = [g, ctx]
+
+        def end(buckets):
+            if cur:
+                cur[1].__exit__(None, None, None)
+                segs.append((cur[0], list(buckets)))
+                cur[:] = []
+            elif buckets:                           # buckets nothing was launched for since the last boundary
+                segs[-1] = (segs[-1][0], segs[-1][1] + list(buckets))
+
+        try:
+            begin()
+            heat = self.forward(gx)
+            self.loss_and_grad(heat, gt, gw)
+            for done in self._backward_walk(self._loss_grad, pre=begin):
+                end(done)
+            end([])                                 # nodes behind the last bucket boundary (they write no parameter gradient)
+        except BaseException:
+            if cur:
+                cur[1].__exit__(None, None, None)
+            raise
+        segs.append((None, []))
+        adam = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(adam, pool=pool):
+            self._adam_step_dev(grad_scale)
+        segs.append((adam, []))
+        return segs
+
+    def train_step(self, x, target, target_weight, world_size=1):
+        """function.py:46-76 for one batch.  Returns the loss tensor fp64 [2] = (L_hm, L_offset) on device."""
+        heat = self.forward(x)
+        loss, d = self.loss_and_grad(heat, target.contiguous(), target_weight.contiguous())
+        self.backward(d, world_size)                       # incl. the one exchange step (SURVEY 8e), bucket by bucket
+        self.adam_step(1.0 / world_size)                   # mean over ranks = grad_scale
+        return loss
+
+
+class HRNetTrainer(Trainer):
+    def __init__(self, cfg, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, psa=False,
+                 bucket_elems=6 * 1024 * 1024):
+        """``psa``: the pose_hrnet_psa variant -- a PSA_s ("<block>.deattn.*") after relu(bn1) of every BasicBlock
+        (pose_hrnet_psa.py:37,49), trained through the udp_psa_train_* entry points.  ``bucket_elems``: gradient elements
+        per all-reduce bucket (the default is ~25 MB)."""
+        from .model import _get
+        self.psa = bool(psa)
+        self.extra = _get(cfg, "MODEL", "EXTRA")
+        num_joints, target_type = int(_get(cfg, "MODEL", "NUM_JOINTS")), _get(cfg, "MODEL", "TARGET_TYPE")
+        shapes = hrnet_param_shapes(self.extra, num_joints, target_type, psa=self.psa)
+        super().__init__(shapes, state_dict, num_joints, target_type, device=device, dtype=dtype, lr=lr, betas=betas, eps=eps,
+                         bucket_elems=bucket_elems)
+        self.bn_multi = os.environ.get("UDP_POSE_NO_BN_MULTI") is None           # A/B knob
+        self.conv_multi = os.environ.get("UDP_POSE_NO_CONV_MULTI") is None       # A/B knob (merged branch convs)
+
+    def _conv_entry(self, key, shape):
+        if ".deattn." in key and not key.endswith(".conv_v_left.weight"):
+            return None             # the attention block reads its small fp32 matrices as they are; only theta is a conv
+        return super()._conv_entry(key, shape)
 
     def _bn_multi(self, xs, names, relu=True, res=None):
         """The BatchNorms `names[b]` over `xs[b]` (one per branch, independent) as ONE multi-tensor call per pass
@@ -570,56 +861,6 @@ class HRNetTrainer:
             outs.append(self._sum_relu(terms))
         return outs
 
-    def _sum_relu(self, terms):
-        """y = relu(sum_k up(term_k, shift_k)): HighResolutionModule.forward :266-272."""
-        L = _lib.lib()
-        t0 = terms[0][0]
-        y = self._new(t0.n, t0.h << terms[0][1], t0.w << terms[0][1], t0.c)
-        # ONE launch: y = relu(((t0 + t1) + t2) + ...), the terms added in the reference's order (udp_conv2d_fused, UDP_OP_FUSE:
-        # in + res + up to three addends, each up-sampled by its shift; shift 0 = same resolution); fp32 tensors: the numbers of
-        # the term-by-term launches below, bit for bit
-        second = len(terms) > 1 and terms[1][1] == 0           # `res` carries no shift
-        rest = terms[2:] if second else terms[1:]
-        if self.fuse_sums and terms[0][1] == 0 and len(rest) <= 3:
-            op = self._conv_op(1, 1, y.ck, y.ck, y.h, y.w, y.h, y.w)
-            op.kind, op.relu, op.n_up = _lib.UDP_OP_FUSE, 1, len(rest)
-            for k, (t, s) in enumerate(rest):
-                op.up_shift[k] = s
-            up_ptrs = [t.buf.data_ptr() for t, _ in rest] + [None] * (3 - len(rest))
-            _lib.check(L.udp_conv2d_fused(C.byref(op), self._dt, y.n, terms[0][0].buf.data_ptr(), None, None,
-                                          terms[1][0].buf.data_ptr() if second else None, up_ptrs[0], up_ptrs[1], up_ptrs[2],
-                                          y.buf.data_ptr(), self._stream()))
-        else:
-            for k, (t, s) in enumerate(terms):
-                _lib.check(L.udp_ew_accumulate(y.buf.data_ptr(), t.buf.data_ptr(), y.n, y.h, y.w, y.ck, s, int(k == 0),
-                                               int(k == len(terms) - 1), self._dt, self._stream()))
-
-        def backward():
-            g = self._like(y)
-            _lib.check(L.udp_relu_bwd(y.grad.data_ptr(), y.buf.data_ptr(), g.data_ptr(), g.numel(), self._dt,
-                                      self._stream()))
-            handed = not self.fuse_sums
-            for t, s in terms:
-                if not t.needs_grad:
-                    continue
-                have = t.grad is not None
-                if s == 0 and not have and not handed:
-                    # the first same-resolution term without a gradient yet takes g itself instead of a copy of it: every
-                    # other term of this sum reads g inside this function, later writers of t.grad come later on the tape
-                    t.grad = g
-                    handed = True
-                    continue
-                if not have:
-                    t.grad = self._like(t)
-                if s == 0:
-                    _lib.check(L.udp_ew_accumulate(t.grad.data_ptr(), g.data_ptr(), t.n, t.h, t.w, t.ck, 0, int(not have),
-                                                   0, self._dt, self._stream()))
-                else:
-                    _lib.check(L.udp_upsample_bwd(g.data_ptr(), y.n, y.h, y.w, y.ck, s, t.grad.data_ptr(), int(have),
-                                                  self._dt, self._stream()))
-        self._tape.append((y, backward, None, []))
-        return y
-
     # ------------------------------------------------------------------ the HRNet graph (pose_hrnet.py)
     def _basic(self, x, p):
         t = self._bn(self._conv(x, p + ".conv1", bn_stats=True), p + ".bn1")
@@ -705,206 +946,138 @@ class HRNetTrainer:
         self._out = self._conv(ys[0], "final_layer", bias_key="final_layer.bias", nchw_out=True)
         return self._out.buf
 
-    def _backward_walk(self, dheat, pre=None):
-        """The tape in reverse.  Yields the list of gradient buckets a backward node has just completed (the node wrote
-        their last gradient), and finally the buckets no node completed (a bucket with an unused parameter: its gradient
-        stays as is).  ``pre()`` is called before anything is launched after a yield (segmented graph capture opens its
-        next segment there).  Every parameter gradient is overwritten (implicit zero_grad)."""
+
+class PoseResNetTrainer(Trainer):
+    """pose_resnet / SimpleBaseline (deep_hrnet/lib/models/pose_resnet.py:105-209; recipe
+    experiments/coco/resnet/res50_256x192_d256x3_adam_lr1e-3.yaml) on the base step.  ``spec``: the dict of
+    ``resnet_plan.pose_resnet_spec`` (``layers`` may be any 4-tuple of Bottleneck counts).  fp32 only: the reference's
+    precision, and the transposed conv has no bf16 form."""
+
+    def __init__(self, spec, num_joints, target_type, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-8, bucket_elems=6 * 1024 * 1024):
+        from .synth_resnet import pose_resnet_param_shapes
+        if dtype != "f32":
+            raise ValueError("pose_resnet trains in fp32 only (dtype %r): the deconv kernels have no bf16 form" % (dtype,))
+        self.spec = dict(spec)
+        if len(self.spec["layers"]) != 4 or any(f % 16 for f in self.spec["deconv_filters"]):
+            raise ValueError("pose_resnet trainer: four stages and deconv filters in multiples of 16 (got %s, %s)"
+                             % (self.spec["layers"], self.spec["deconv_filters"]))
+        shapes = pose_resnet_param_shapes(layers=tuple(self.spec["layers"]), num_joints=int(num_joints),
+                                          deconv_filters=tuple(self.spec["deconv_filters"]), deconv_kernel=4,
+                                          final_kernel=self.spec["final_kernel"],
+                                          deconv_with_bias=self.spec["deconv_with_bias"])
+        super().__init__(shapes, state_dict, num_joints, target_type, device=device, dtype=dtype, lr=lr, betas=betas, eps=eps,
+                         bucket_elems=bucket_elems)
+
+    def _conv_entry(self, key, shape):
+        if key.startswith("deconv_layers."):
+            return shape[1], shape[0], shape[2], True, True       # ConvTranspose2d.weight is [cin][cout][k][k]
+        return super()._conv_entry(key, shape)
+
+    # ------------------------------------------------------------------ the ops HRNet does not have
+    def _stem(self, x):
+        """conv1 (:112, :196): 3 -> 64, 7x7 stride 2 on the unfolded weights.  No input gradient: x is the image."""
         L = _lib.lib()
-        if pre:
-            pre()
-        o = self._out
-        g = torch.empty(o.n * o.h * o.w * o.ck, dtype=self._tdt, device=self.device)
-        _lib.check(L.udp_nchw_to_nhwc(dheat.data_ptr(), o.n, o.c, o.h, o.w, o.ck, g.data_ptr(), self._dt, self._stream()))
-        o.grad = g
-        left = [c for _, _, c in self._buckets]
-        for y, bwd, _, keys in reversed(self._tape):
-            done = []
-            if y.grad is not None:
-                if pre:
-                    pre()
-                bwd()
-                for k in keys:
-                    b = self._bucket_of[k]
-                    left[b] -= 1
-                    if left[b] == 0:
-                        done.append(b)
-            y.grad = None
-            if done:
-                self._join_side()             # the bucket's weight gradients were written on the side stream
-                yield done
+        cout, cin, ks, wf, _ = self._convs["conv1"]
+        ho, wo = (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1
+        y = self._new(x.n, ho, wo, cout)
+        _lib.check(L.udp_stem7_train_fwd(x.buf.data_ptr(), wf.data_ptr(), x.n, x.h, x.w, x.ck, cout, self._dt,
+                                         y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            dy = y.grad
+            self._on_side(lambda: _lib.check(L.udp_conv2d_wgrad(
+                x.buf.data_ptr(), dy.data_ptr(), x.n, x.h, x.w, x.ck, ho, wo, y.ck, ks, 2, cout, cin, self._dt,
+                self._g("conv1.weight"), 0, self._wgrad_ws.data_ptr(), self._wgrad_ws.numel(), self._stream())), dy, x.buf)
+        self._tape.append((y, backward, None, ["conv1.weight"]))
+        return y
+
+    def _maxpool(self, x):
+        """MaxPool2d(3, 2, 1) (:116, :199)."""
+        L = _lib.lib()
+        y = self._new(x.n, (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1, x.c)
+
+        _lib.check(L.udp_maxpool3s2_fwd(x.buf.data_ptr(), x.n, x.h, x.w, x.ck, self._dt, y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            if x.grad is not None:
+                raise RuntimeError("max-pool: its input has one consumer")
+            x.grad = self._like(x)
+            _lib.check(L.udp_maxpool3s2_bwd(x.buf.data_ptr(), y.grad.data_ptr(), x.n, x.h, x.w, x.ck, self._dt,
+                                            x.grad.data_ptr(), self._stream()))
+        self._tape.append((y, backward, None, []))
+        return y
+
+    def _deconv(self, x, name, bias_key=None):
+        """ConvTranspose2d(4, 2, 1) (:155-193): forward = the UDP_OP_DECONV kernel on the packed raw weights, weight
+        gradient = udp_conv2d_wgrad with ks 4 (dY as its `x`, the input as its `dy`), input gradient =
+        udp_deconv4s2_dgrad.  The head is a chain: the input has no other consumer."""
+        L = _lib.lib()
+        cout, cin, ks, wf, wd = self._convs[name]
+        if x.c != cin or x.c != x.ck:
+            raise ValueError("%s: expects %d input channels (a multiple of 16), got %d" % (name, cin, x.c))
+        y = self._new(x.n, 2 * x.h, 2 * x.w, cout)
+        op = self._conv_op(4, 2, x.ck, cout, x.h, x.w, y.h, y.w)
+        op.kind = _lib.UDP_OP_DECONV
+        bias, keep = self._zeros.data_ptr(), None
+        if bias_key:                                       # bias row padded to cout_pad
+            keep = torch.zeros(_rup(cout, 32), dtype=torch.float32, device=self.device)
+            keep[:cout] = self.param(bias_key)
+            bias = keep.data_ptr()
+        _lib.check(L.udp_conv2d_fused(C.byref(op), self._dt, x.n, x.buf.data_ptr(), wf.data_ptr(), bias, None, None, None,
+                                      None, y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            dy = y.grad                                    # NHWC [n,2h,2w,cout]
+
+            def wgrad():
+                _lib.check(L.udp_conv2d_wgrad(dy.data_ptr(), x.buf.data_ptr(), x.n, y.h, y.w, y.ck, x.h, x.w, x.ck, 4, 2,
+                                              cin, cout, self._dt, self._g(name + ".weight"), 0,
+                                              self._wgrad_ws.data_ptr(), self._wgrad_ws.numel(), self._stream()))
+                if bias_key:
+                    _lib.check(L.udp_bias_grad(dy.data_ptr(), y.n * y.h * y.w, y.ck, cout, self._g(bias_key), self._dt,
+                                               self._stream()))
+            self._on_side(wgrad, dy, x.buf)
+            if not x.needs_grad:
+                return
+            if x.grad is not None:
+                raise RuntimeError("%s: its input has one consumer" % name)
+            x.grad = self._like(x)
+            _lib.check(L.udp_deconv4s2_dgrad(dy.data_ptr(), wd.data_ptr(), x.n, x.h, x.w, cin, x.ck, cout, y.ck, self._dt,
+                                             x.grad.data_ptr(), self._stream()))
+        self._tape.append((y, backward, keep, [name + ".weight"] + ([bias_key] if bias_key else [])))
+        return y
+
+    # ------------------------------------------------------------------ the graph (pose_resnet.py:195-209)
+    def _bottleneck(self, x, p, stride):
+        """Bottleneck.forward (:82-100) as _make_layer builds it (:138-153): the stride sits on conv2 and on the 1x1
+        projection shortcut."""
+        a = self._bn(self._conv(x, p + ".conv1", bn_stats=True), p + ".bn1")
+        b = self._bn(self._conv(a, p + ".conv2", stride=stride, bn_stats=True), p + ".bn2")
+        r = x
+        if (p + ".downsample.0") in self._convs:
+            r = self._bn(self._conv(x, p + ".downsample.0", stride=stride, bn_stats=True), p + ".downsample.1", relu=False)
+        return self._bn(self._conv(b, p + ".conv3", bn_stats=True), p + ".bn3", res=r)
+
+    def forward(self, x):
+        """Train-mode forward.  x: fp32 [N,3,H,W] on the device.  Returns fp32 [N,J,H/4,W/4]."""
+        L = _lib.lib()
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+            raise ValueError("expected contiguous fp32 [N,3,H,W]")
+        n, _, h, w = x.shape
+        if h % 32 or w % 32:
+            raise ValueError("input %dx%d must be a multiple of 32" % (h, w))
         self._tape = []
-        self._join_side()
-        rest = [b for b, n_left in enumerate(left) if n_left > 0]
-        if rest:
-            yield rest
-
-    def backward(self, dheat, world_size=1):
-        """dheat: fp32 [N,C,h,w] = d loss / d heat-maps.  Fills self.grad (zero_grad is implicit: every
-        parameter gradient is overwritten).  ``world_size > 1``: every gradient bucket is SUM-all-reduced
-        (asynchronously, on the communication stream of torch.distributed) as soon as its last gradient has been
-        written, overlapping the rest of the backward; on return all buckets are reduced."""
-        works = []
-        self.reduce_order = []                # bucket indices in the order their all-reduce was issued
-        for done in self._backward_walk(dheat):
-            if world_size > 1:
-                works += [self._reduce_bucket(b) for b in done]
-        for w in works:
-            w.wait()
-
-    def _reduce_bucket(self, b):
-        from .dist import allreduce_sum_async
-        lo, hi, _ = self._buckets[b]
-        self.reduce_order.append(b)
-        if os.environ.get("UDP_POSE_FAKE_ALLREDUCE"):        # timing diagnosis only (tools/bench_train.py): no exchange
-            class _Done:
-                def wait(self):
-                    return True
-            return _Done()
-        return allreduce_sum_async(self.grad[lo:hi])
-
-    def loss_and_grad(self, heat, target, target_weight):
-        """criterion(output, target, target_weight) (loss.py:15-76) and its gradient w.r.t. output."""
-        b, c = heat.shape[:2]
-        off = self.target_type == "offset"
-        j = c // 3 if off else c
-        d = torch.empty_like(heat)
-        _lib.check(_lib.lib().udp_mse_loss(heat.data_ptr(), target.data_ptr(), target_weight.data_ptr(), b, j,
-                                           heat.shape[2] * heat.shape[3], int(off), self._loss.data_ptr(), d.data_ptr(),
-                                           self._stream()))
-        self._loss_grad = d
-        return self._loss, d
-
-    def adam_step(self, grad_scale=1.0):
-        """optimizer.step(): torch.optim.Adam(lr) on the flat parameter buffer (utils.py:70-74).
-        ``grad_scale``: 1/world_size after the SUM all-reduce of the gradient."""
-        self.step_count += 1
-        self.version += 1                                   # owners compare it with the version they last read
-        _lib.check(_lib.lib().udp_adam_step(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                            self.exp_avg_sq.data_ptr(), self._n_param, self.lr, self.betas[0],
-                                            self.betas[1], self.eps, self.step_count, float(grad_scale),
-                                            self._stream()))
-
-    def _adam_step_dev(self, grad_scale=1.0):
-        _lib.check(_lib.lib().udp_adam_step_dev(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                                self.exp_avg_sq.data_ptr(), self._n_param, self.betas[0], self.betas[1],
-                                                self.eps, self._coef.data_ptr(), float(grad_scale), self._stream()))
-
-    def train_step_graphed(self, x, target, target_weight, world_size=1):
-        """train_step with the whole step (weight packing, forward, criterion, backward, Adam: ~1900
-        launches issued from the Python tape) captured ONCE per input shape as a hipGraph (torch.cuda.graph: stream
-        capture of our launches on torch's capture stream, activations from the graph's private pool) and replayed:
-        the host then costs one graph launch per step instead of one ctypes call per kernel.  The first step of a
-        shape runs eagerly (lazy one-time initialisation must not be captured), the second captures and replays.
-        Arithmetic and results are those of train_step, bit for bit; the learning rate may change between steps
-        (it only enters through Adam's two scalars, uploaded before every replay), betas / eps are part of the key.
-        At most two shapes stay captured (a full and a ragged last batch).
-
-        ``world_size > 1`` (one process per GPU, config 3): the step is captured in SEGMENTS that end where a gradient
-        bucket receives its last gradient -- forward + criterion + the backward of the last layers; the backward
-        between two bucket boundaries; ...; and Adam on its own.  A replayed step is: replay segment 0, issue the
-        asynchronous SUM all-reduce of its bucket(s) from the host (torch.distributed orders it behind the segment on
-        its communication stream: RCCL over xGMI, or gloo), replay segment 1 at once -- the exchange runs under it, as
-        DistributedDataParallel's reducer overlaps the reference's backward -- and so on; the work handles are waited
-        for (stream order, no host block under RCCL) before the Adam graph with grad_scale 1 / world_size.  All
-        segments share one memory pool and are always replayed in capture order.  Same arithmetic, same bucket order
-        and the same results as train_step(world_size), bit for bit."""
-        key = (tuple(x.shape), tuple(target.shape), tuple(target_weight.shape), self.betas, self.eps, int(world_size))
-        ent = self._graphs.get(key)
-        if ent is None:
-            if key not in self._warm:                                # first step of this shape: eager
-                self._warm.add(key)
-                return self.train_step(x, target, target_weight, world_size=world_size)
-            if self._coef is None:
-                self._coef = torch.zeros(2, dtype=torch.float32, device=self.device)
-                # pinned staging slots for the asynchronous upload of Adam's two scalars: the host runs steps ahead
-                # of the GPU, a slot is rewritten only after the copy that read it has completed (its event)
-                self._coef_host = [torch.zeros(2, dtype=torch.float32).pin_memory() for _ in range(4)]
-                self._coef_done = [None] * 4
-            gx, gt, gw = x.clone(), target.contiguous().clone(), target_weight.contiguous().clone()
-            torch.cuda.synchronize()             # the last replay of an evicted graph may still be running
-            while len(self._graphs) >= 2:
-                self._graphs.pop(next(iter(self._graphs)))
-            if world_size == 1:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    heat = self.forward(gx)
-                    self.loss_and_grad(heat, gt, gw)
-                    self.backward(self._loss_grad)
-                    self._adam_step_dev()
-                segs = [(graph, [])]
-            else:
-                segs = self._capture_segments(gx, gt, gw, 1.0 / world_size)
-            ent = self._graphs[key] = (segs, gx, gt, gw)
-        segs, gx, gt, gw = ent
-        gx.copy_(x, non_blocking=True)
-        gt.copy_(target, non_blocking=True)
-        gw.copy_(target_weight, non_blocking=True)
-        self.step_count += 1
-        slot = self.step_count % 4
-        if self._coef_done[slot] is not None:
-            self._coef_done[slot].synchronize()
-        _lib.check(_lib.lib().udp_adam_coefficients(self.lr, self.betas[0], self.betas[1], self.step_count,
-                                                    self._coef_host[slot].data_ptr()))
-        self._coef.copy_(self._coef_host[slot], non_blocking=True)
-        self._coef_done[slot] = torch.cuda.Event()
-        self._coef_done[slot].record()
-        works = []
-        self.reduce_order = []
-        for graph, buckets in segs:
-            if graph is None:                                        # every bucket is reduced: Adam may read the gradient
-                for w in works:
-                    w.wait()
-                continue
-            graph.replay()
-            works += [self._reduce_bucket(b) for b in buckets]
-        self.version += 1
-        return self._loss
-
-    def _capture_segments(self, gx, gt, gw, grad_scale):
-        """The step as a list of (graph, buckets to all-reduce after it) in replay order, a (None, []) marker where
-        the outstanding all-reduces must be waited for, and the Adam graph last."""
-        pool = torch.cuda.graph_pool_handle()
-        segs = []
-        cur = []                                    # [graph, context] of the segment being captured, or empty
-
-        def begin():
-            if not cur:
-                g = torch.cuda.CUDAGraph()
-                ctx = torch.cuda.graph(g, pool=pool)
-                ctx.__enter__()
-                cur[:] = [g, ctx]
-
-        def end(buckets):
-            if cur:
-                cur[1].__exit__(None, None, None)
-                segs.append((cur[0], list(buckets)))
-                cur[:] = []
-            elif buckets:                           # buckets nothing was launched for since the last boundary
-                segs[-1] = (segs[-1][0], segs[-1][1] + list(buckets))
-
-        try:
-            begin()
-            heat = self.forward(gx)
-            self.loss_and_grad(heat, gt, gw)
-            for done in self._backward_walk(self._loss_grad, pre=begin):
-                end(done)
-            end([])                                 # nodes behind the last bucket boundary (they write no parameter gradient)
-        except BaseException:
-            if cur:
-                cur[1].__exit__(None, None, None)
-            raise
-        segs.append((None, []))
-        adam = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(adam, pool=pool):
-            self._adam_step_dev(grad_scale)
-        segs.append((adam, []))
-        return segs
-
-    def train_step(self, x, target, target_weight, world_size=1):
-        """function.py:46-76 for one batch.  Returns the loss tensor fp64 [2] = (L_hm, L_offset) on device."""
-        heat = self.forward(x)
-        loss, d = self.loss_and_grad(heat, target.contiguous(), target_weight.contiguous())
-        self.backward(d, world_size)                       # incl. the one exchange step (SURVEY 8e), bucket by bucket
-        self.adam_step(1.0 / world_size)                   # mean over ranks = grad_scale
-        return loss
+        _lib.check(L.udp_pack_conv_weights_batch(self._pack_table.data_ptr(), len(self._convs), self._dt, self._stream()))
+        a = self._new(n, h, w, 3, needs_grad=False)
+        _lib.check(L.udp_nchw_to_nhwc(x.data_ptr(), n, 3, h, w, a.ck, a.buf.data_ptr(), self._dt, self._stream()))
+        a = self._maxpool(self._bn(self._stem(a), "bn1"))
+        for li, nblk in enumerate(self.spec["layers"], start=1):
+            for k in range(nblk):
+                a = self._bottleneck(a, "layer%d.%d" % (li, k), 2 if (li > 1 and k == 0) else 1)
+        for d in range(len(self.spec["deconv_filters"])):
+            q = "deconv_layers.%d" % (3 * d)
+            a = self._bn(self._deconv(a, q, q + ".bias" if self.spec["deconv_with_bias"] else None),
+                         "deconv_layers.%d" % (3 * d + 1))
+        self._out = self._conv(a, "final_layer", bias_key="final_layer.bias", nchw_out=True)
+        return self._out.buf
