@@ -802,6 +802,74 @@ int udp_stem7_train_fwd(const void* x, const void* w_fwd, int n, int h, int w, i
                         void* y, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Training of the ShuffleNetV2 pose nets (pose_shufflenetv2_10x_pixel_shuffle,
+ * pose_shufflenetv2_10x; recipes experiments/coco/shufflenetv2/): the ops their
+ * graph has beyond the two steps above (csrc/shufflenet_train.hip).  fp32 only
+ * (UDP_F32; anything else is UDP_ERR_UNSUPPORTED).  Symbols only:
+ * UDP_POSE_ABI_VERSION stays as it is.
+ *
+ * All tensors are NHWC with a stored channel count that is a multiple of 4 (a thread owns 4 consecutive channels and
+ * moves 16 bytes).  Every entry point writes EVERY stored channel of its outputs -- padded channels come out as zeros
+ * computed from zeros --, uses no atomics, and sums in one order that depends on the shape alone: eager and captured
+ * steps are bit-equal, and so are two runs.
+ * ------------------------------------------------------------------------- */
+/* Depthwise 3x3 conv, stride 1 | 2, padding 1, no bias, no activation (shufflenetv2.py:54 branch_main.3, :66
+ * branch_proj.0 under model.train(); the BatchNorm that follows stays unfolded):
+ *   y[n,oy,ox,ch] = sum_{ky,kx} x[n, oy*s+ky-1, ox*s+kx-1, ch] * w[ch][0][ky][kx]
+ * as nine fmaf in (ky, kx) order with the taps outside the image skipped -- the contract of the inference kernel
+ * (UDP_OP_DWCONV).  x: [n,hin,win,c]; w: the parameter itself, [c_real][1][3][3] fp32, read in place (no pack step),
+ * 16-byte aligned; c_real <= c, channels c_real..c of y are written as zero.  y: [n,hout,wout,c] with
+ * hout = (hin-1)/s + 1 (odd sizes allowed).  Stride other than 1 | 2: UDP_ERR_UNSUPPORTED. */
+int udp_dwconv3_train_fwd(const void* x, const void* w, int n, int hin, int win, int c, int c_real, int stride, int dtype,
+                          void* y, void* stream);
+/* Its input gradient (autograd's backward of :54 / :66 w.r.t. the input):
+ *   dx[n,iy,ix,ch] (+)= sum_{ky,kx} dy[n, (iy+1-ky)/s, (ix+1-kx)/s, ch] * w[ch][ky][kx]
+ * over the taps where the division is exact and the index lies inside dy [n,hout,wout,c].  A gather: one thread owns an
+ * input pixel x 4 channels.  `accumulate` != 0 adds the sum to dx (the input of a stride-2 unit feeds both branches,
+ * :81-84); otherwise every element of dx [n,hin,win,c] is overwritten. */
+int udp_dwconv3_dgrad(const void* dy, const void* w, int n, int hin, int win, int c, int c_real, int stride, int accumulate,
+                      int dtype, void* dx, void* stream);
+/* Its weight gradient, written in the parameter layout [c_real][1][3][3] (nothing is accumulated):
+ *   dw[ch][ky][kx] = sum_{n,y,x} dy[n,y,x,ch] * x[n, y*s+ky-1, x*s+kx-1, ch]
+ * Two launches.  The n*hout output rows are cut into `partials` runs of `rows` consecutive rows; a workgroup takes one
+ * run and up to 64 channel groups (lanes along channels, 9 taps x 4 channels of fp32 accumulators per thread, its pixel
+ * lanes combined through LDS in lane order) and leaves a [9][c] partial in the workspace; the second launch adds the
+ * partials in index order.  partials = min(n*hout, 256, workspace_bytes / (36 c)), rows = ceil(n*hout / partials),
+ * partials = ceil(n*hout / rows): a pure function of the shape and the workspace size.  A workspace that holds no
+ * partial: UDP_ERR_WORKSPACE.  udp_dwconv3_wgrad_workspace_bytes: what the unconstrained split needs (0: bad shape);
+ * never more than 256 * 36 * c bytes, which (n = 256, hout = 1) returns. */
+size_t udp_dwconv3_wgrad_workspace_bytes(int n, int hout, int wout, int c);
+int udp_dwconv3_wgrad(const void* x, const void* dy, int n, int hin, int win, int c, int c_real, int stride, int dtype,
+                      void* dw, void* workspace, size_t workspace_bytes, void* stream);
+/* Host only: the split udp_dwconv3_wgrad would use (it calls the same function).  out[0] = output rows per workgroup,
+ * out[1] = workgroups of the first launch (partials x channel blocks), out[2] = partials, out[3] = LDS bytes of a
+ * workgroup.  Returns what the launch would return for this shape and workspace. */
+int udp_debug_dw_wgrad_plan(int n, int hout, int wout, int c, size_t workspace_bytes, int* out);
+/* nn.PixelShuffle(2) in torch's own channel order (decoders/DUC.py:27 under model.train()) and its backward:
+ *   y[n, 2h+i, 2w+j, ch] = x[n, h, w, 4ch + 2i + j]          x: [n,h,w,cin], y: [n,2h,2w,cin/4]
+ * _bwd is the inverse: dy [n,2h,2w,cin/4] -> dx [n,h,w,cin]; h, w, cin describe the LOW-resolution tensor in both.
+ * (The inference op UDP_OP_PIXSHUF assumes the planner's permuted conv groups; a trainer keeps the parameter order.)
+ * cin % 64 == 0.  Pure data movement: bit patterns are never decoded. */
+int udp_pixshuf2_train_fwd(const void* x, int n, int h, int w, int cin, int dtype, void* y, void* stream);
+int udp_pixshuf2_train_bwd(const void* dy, int n, int h, int w, int cin, int dtype, void* dx, void* stream);
+/* torch.cat + channel_shuffle of ShuffleV2Block.forward (shufflenetv2.py:77-92) without the concat.  A unit's output is
+ * a pair (a, b) of [m][in_pitch] tensors with r real channels each; logical channel j of the concat is a[j] for j < r,
+ * else b[j-r].  even[k] = logical[2k], odd[k] = logical[2k+1] for k < r and zeros for r <= k < cp; even / odd:
+ * [m][cp], cp % 4 == 0.  r need not be a multiple of 4 (58 at 1.0x): elements are read one by one, stores are 16 bytes.
+ * _bwd is the inverse permutation of (d_even, d_odd) [m][cp] into (d_a, d_b) [m][out_pitch], pads zero. */
+int udp_shuffle_pair_fwd(const void* a, const void* b, int64_t m, int r, int in_pitch, int cp, int dtype, void* even,
+                         void* odd, void* stream);
+int udp_shuffle_pair_bwd(const void* d_even, const void* d_odd, int64_t m, int r, int cp, int out_pitch, int dtype,
+                         void* d_a, void* d_b, void* stream);
+/* The materialised concat where a whole unit tensor is read (the input of a stride-2 unit, :81-84, and of conv_last,
+ * :143): y[:, :ra] = a, y[:, ra:ra+rb] = b, zeros up to c; a: [m][pa], b: [m][pb], y: [m][c], c % 4 == 0.
+ * udp_chan_uncat2 is its inverse (and its backward): a = y[:, :ra], b = y[:, ra:ra+rb], pads zero; pa, pb % 4 == 0. */
+int udp_chan_cat2(const void* a, int pa, int ra, const void* b, int pb, int rb, int64_t m, int c, int dtype, void* y,
+                  void* stream);
+int udp_chan_uncat2(const void* y, int c, int64_t m, int dtype, void* a, int pa, int ra, void* b, int pb, int rb,
+                    void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Training of the polarized self-attention block of pose_hrnet_psa.  Replaces
  * PSA_s.forward (deep_hrnet/lib/models/PSA.py:190-269: spatial_pool :190-222,
  * channel_pool :224-258) under model.train() and its autograd backward.

@@ -163,6 +163,19 @@ _SIGS = {
     "udp_maxpool3s2_fwd": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P]),
     "udp_maxpool3s2_bwd": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P]),
     "udp_stem7_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
+    # training of the ShuffleNetV2 pose nets: depthwise 3x3 forward / dgrad / wgrad, pixel shuffle, channel shuffle on
+    # pairs of halves, concat (csrc/shufflenet_train.hip)
+    "udp_dwconv3_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
+    "udp_dwconv3_dgrad": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P]),
+    "udp_dwconv3_wgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "udp_dwconv3_wgrad": (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P, C.c_size_t, _P]),
+    "udp_debug_dw_wgrad_plan": (C.c_int, [C.c_int] * 4 + [C.c_size_t, C.POINTER(C.c_int)]),
+    "udp_pixshuf2_train_fwd": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P]),
+    "udp_pixshuf2_train_bwd": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P]),
+    "udp_shuffle_pair_fwd": (C.c_int, [_P, _P, C.c_int64] + [C.c_int] * 4 + [_P, _P, _P]),
+    "udp_shuffle_pair_bwd": (C.c_int, [_P, _P, C.c_int64] + [C.c_int] * 4 + [_P, _P, _P]),
+    "udp_chan_cat2": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    "udp_chan_uncat2": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
     # training of the polarized self-attention block (pose_hrnet_psa)
     "udp_psa_train_save_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "udp_psa_train_fwd_pool": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),

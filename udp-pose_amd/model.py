@@ -69,7 +69,8 @@ class PoseNetHip:
         return dict(self._sd or {})
 
     def trainer(self):
-        raise NotImplementedError("%s: the training step covers pose_hrnet, pose_hrnet_psa and pose_resnet only" % self.NAME)
+        raise NotImplementedError("%s: the training step covers pose_hrnet, pose_hrnet_psa, pose_resnet and the two "
+                                  "ShuffleNetV2 nets only" % self.NAME)
 
     def to(self, device):
         self.device = torch.device(device)
@@ -535,16 +536,20 @@ def get_pose_net_resnet_psa(cfg, is_train, **kwargs):
     return PoseResNetPsaHip(cfg, **kwargs)
 
 
-class PoseShuffleNetV2Hip(PoseNetHip):
+class PoseShuffleNetV2Hip(_Trainable, PoseNetHip):
     """pose_shufflenetv2_10x_pixel_shuffle (deep_hrnet/lib/models/pose_shufflenetv2_10x_pixel_shuffle.py:23-53: the
-    ShuffleNetV2 0.5x / 1.0x / 1.5x backbone, the pixel-shuffle (DUC) decoder, ``final_layer``) inference through the
-    same C ABI; ``state_dict`` in the reference module's key format.  Storage modes "f32" and "f16x2" (the depthwise
-    kernel has no bf16 form)."""
+    ShuffleNetV2 0.5x / 1.0x / 1.5x backbone, the pixel-shuffle (DUC) decoder, ``final_layer``) through the same C ABI;
+    ``state_dict`` in the reference module's key format.  Storage modes "f32" and "f16x2" (the depthwise kernel has no
+    bf16 form).  ``trainable`` (what ``MODELS[NAME](cfg, is_train=True)`` sets): the model also has the training surface
+    of ``PoseResNetHip`` -- ``init_weights``, ``train()``, ``parameters()``, ``trainer()`` (a train.ShuffleNetV2Trainer,
+    fp32 whatever the storage mode of the inference program)."""
 
     NAME = "pose_shufflenetv2_10x_pixel_shuffle"
     DTYPES = ("f32", "f16x2")
+    TRAINS = True                # a net of this class can be built trainable
+    TRAINER = "ShuffleNetV2Trainer"
 
-    def __init__(self, cfg, dtype="f32"):
+    def __init__(self, cfg, dtype="f32", trainable=False):
         if dtype not in self.DTYPES:
             raise ValueError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
         super().__init__(cfg, dtype)
@@ -552,6 +557,7 @@ class PoseShuffleNetV2Hip(PoseNetHip):
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
         self.spec = self._spec_of(self.extra, self.num_joints, self.target_type)   # NotImplementedError for 2.0x ...
+        self.trainable = bool(trainable) and self.TRAINS
 
     @staticmethod
     def _spec_of(extra, num_joints, target_type):
@@ -566,17 +572,86 @@ class PoseShuffleNetV2Hip(PoseNetHip):
                                        final_kernel=sp["final_kernel"])
 
     def init_weights(self, pretrained=""):
-        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+        """What the reference's constructor leaves behind (the pose modules have no ``init_weights`` of their own).  The
+        backbone is ``ShuffleNetV2._initialize_weights`` (backbones/shufflenetv2.py:168-190): the first conv ~ N(0, 0.01),
+        every other conv ~ N(0, 1 / cin_per_group), BatchNorm weight 1, bias 1e-4, running mean 0, the classifier ~
+        N(0, 0.01).  Decoder / deconv head / ``final_layer`` keep torch's nn.Conv2d / ConvTranspose2d / BatchNorm2d
+        defaults (kaiming_uniform(a = sqrt 5) = U(+-1 / sqrt(fan_in)), the same bound for a bias; BatchNorm 1 / 0).  A
+        ``pretrained`` file is read like ``load_checkpoint`` (:6-31): ``checkpoint["state_dict"]``, ``module.`` stripped,
+        the keys are the backbone's own (no ``backbone.`` prefix), non-strict -- a tensor of another size keeps its
+        initialised value.  Draws come from torch's global generator."""
+        import math
+        import os
+        if not self.trainable:
+            raise NotImplementedError("%s: built with is_train=False (inference only); load a state_dict" % self.NAME)
+        shapes = self.param_shapes()
+        sd = {}
+        for k, shape in shapes.items():
+            backbone = k.startswith("backbone.")
+            bn = (k.rsplit(".", 1)[0] + ".running_mean") in shapes
+            if k.endswith("num_batches_tracked"):
+                sd[k] = torch.zeros((), dtype=torch.int64)
+            elif k.endswith("running_var"):
+                sd[k] = torch.ones(shape)
+            elif k.endswith("running_mean"):
+                sd[k] = torch.zeros(shape)
+            elif bn:
+                sd[k] = torch.ones(shape) if k.endswith(".weight") else torch.full(shape, 1e-4 if backbone else 0.0)
+            elif backbone and len(shape) == 4:
+                sd[k] = torch.randn(shape) * (0.01 if "first" in k else 1.0 / shape[1])
+            elif backbone:
+                sd[k] = torch.randn(shape) * 0.01             # the classifier's Linear (no bias)
+            else:                                             # nn.Conv2d / nn.ConvTranspose2d defaults, weight before bias
+                w = shapes[k.rsplit(".", 1)[0] + ".weight"]
+                bound = 1.0 / math.sqrt(w[1] * w[2] * w[3])   # (ConvTranspose2d: torch takes fan_in from dim 1 there too)
+                sd[k] = (torch.rand(shape) * 2 - 1) * bound
+        if pretrained and os.path.isfile(pretrained):
+            ckpt = torch.load(pretrained, map_location="cpu", weights_only=True)["state_dict"]
+            for name, v in ckpt.items():
+                name = "backbone." + (name[7:] if name.startswith("module.") else name)
+                if name in sd and tuple(v.shape) == tuple(sd[name].shape):
+                    sd[name] = v                              # non-strict: a missing or differently sized tensor keeps its init
+        return self._set_weights(sd)
+
+    def trainer(self):
+        if not self.trainable:
+            if not self.TRAINS:
+                return PoseNetHip.trainer(self)
+            raise NotImplementedError("%s: built with is_train=False (inference only); MODELS[%r](cfg, is_train=True) "
+                                      "returns the trainable model" % (self.NAME, self.NAME))
+        return super().trainer()
+
+    def _make_trainer(self):
+        from . import train
+        return getattr(train, self.TRAINER)(self.spec, self.num_joints, self.target_type, self._sd, device=self.device,
+                                            dtype="f32")
 
     def _make_program(self, h, w):
         from .shufflenet_plan import ShuffleNetV2Program
         return ShuffleNetV2Program(self._sd, self.spec, h, w, self.dtype)
 
 
+def _init_under_is_train(model, cfg, is_train):
+    """``if is_train and cfg.MODEL.INIT_WEIGHTS: model.init_weights(cfg.MODEL.PRETRAINED)`` of the reference's factories."""
+    if is_train:
+        try:
+            init = bool(_get(cfg, "MODEL", "INIT_WEIGHTS"))
+        except (KeyError, AttributeError):
+            init = False
+        if init:
+            try:
+                pretrained = _get(cfg, "MODEL", "PRETRAINED")
+            except (KeyError, AttributeError):
+                pretrained = ""
+            model.init_weights(pretrained or "")
+    return model
+
+
 def get_pose_net_shufflenetv2(cfg, is_train, **kwargs):
-    """pose_shufflenetv2_10x_pixel_shuffle.py:56-65 (``get_pose_net``); inference only -- the weights come from
-    ``load_state_dict`` (the reference loads ImageNet weights under is_train; training is out of scope)."""
-    return PoseShuffleNetV2Hip(cfg, **kwargs)
+    """pose_shufflenetv2_10x_pixel_shuffle.py:56-65 (``get_pose_net``): trainable under ``is_train``
+    (``init_weights(cfg.MODEL.PRETRAINED)`` when cfg.MODEL.INIT_WEIGHTS says so); otherwise the weights come from
+    ``load_state_dict``."""
+    return _init_under_is_train(PoseShuffleNetV2Hip(cfg, trainable=bool(is_train), **kwargs), cfg, is_train)
 
 
 class PoseShuffleNetV2PlusHip(PoseNetHip):
@@ -716,6 +791,7 @@ class PoseShuffleNetV2DeconvHip(PoseShuffleNetV2Hip):
     MODEL_SIZE refusals."""
 
     NAME = "pose_shufflenetv2_10x"
+    TRAINER = "ShuffleNetV2DeconvTrainer"
 
     @staticmethod
     def _spec_of(extra, num_joints, target_type):
@@ -731,8 +807,8 @@ class PoseShuffleNetV2DeconvHip(PoseShuffleNetV2Hip):
 
 
 def get_pose_net_shufflenetv2_deconv(cfg, is_train, **kwargs):
-    """pose_shufflenetv2_10x.py:100-109 (``get_pose_net``); inference only -- the weights come from ``load_state_dict``."""
-    return PoseShuffleNetV2DeconvHip(cfg, **kwargs)
+    """pose_shufflenetv2_10x.py:100-109 (``get_pose_net``): trainable under ``is_train``, like the pixel-shuffle net."""
+    return _init_under_is_train(PoseShuffleNetV2DeconvHip(cfg, trainable=bool(is_train), **kwargs), cfg, is_train)
 
 
 class PoseShuffleNetV2PlusDeconvHip(PoseShuffleNetV2PlusHip):

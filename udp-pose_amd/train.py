@@ -4,7 +4,8 @@
 the gradient of the whole model is ONE contiguous bucket for the RCCL all-reduce), keeps the tape
 of the train-mode forward its subclass runs op by op through the C ABI, walks it backwards
 (``loss.backward()``), then ``udp_adam_step`` (``optimizer.step()``).  ``HRNetTrainer`` is the graph of
-lib/models/pose_hrnet.py:436-471 (and pose_hrnet_psa), ``PoseResNetTrainer`` that of lib/models/pose_resnet.py:195-209.
+lib/models/pose_hrnet.py:436-471 (and pose_hrnet_psa), ``PoseResNetTrainer`` that of lib/models/pose_resnet.py:195-209,
+``ShuffleNetV2Trainer`` / ``ShuffleNetV2DeconvTrainer`` those of the two ShuffleNetV2 pose nets.
 torch is used for device memory only; every arithmetic step is a kernel of libudp_pose_hip.so.
 
 Reference contract mirrored: ``JointsMSELoss`` / ``JointsMSELoss_offset`` (lib/core/loss.py),
@@ -64,7 +65,7 @@ class _Group:
 
 class Trainer:
     """Everything of the training step that is not one net's graph: the flat parameter / gradient / Adam buffers, the
-    pack table, the primitive ops with their tape entries (``_conv``, ``_bn``, ``_sum_relu``), the backward walk with
+    pack table, the primitive ops with their tape entries (``_conv``, ``_bn``, ``_sum_relu``, ``_maxpool``, ``_deconv``), the backward walk with
     its gradient buckets, the criterion, Adam and the captured step.  A subclass supplies ``forward`` (which fills
     ``self._tape`` and sets ``self._out``) and may override ``_conv_entry``."""
 
@@ -90,7 +91,7 @@ class Trainer:
         self._off, n = {}, 0
         for k in self._keys + self._stat_keys:
             self._off[k] = n
-            n += _rup(int(np.prod(shapes[k])), 4)
+            n += self._key_stride(k, int(np.prod(shapes[k])))
         self._n_param = self._off[self._stat_keys[0]] if self._stat_keys else n
         flat = torch.zeros(n, dtype=torch.float32)
         for k in self._keys + self._stat_keys:
@@ -165,6 +166,12 @@ class Trainer:
             if end - lo >= self.bucket_elems or i + 1 == len(self._keys):
                 self._buckets.append((lo, end, cnt))
                 lo, cnt = end, 0
+
+    bn_over_stored = False       # _bn runs over the stored channels ck of a tensor with c < ck (needs _key_stride % 16 for 1-d keys)
+
+    def _key_stride(self, key, numel):
+        """Floats the tensor ``key`` occupies in ``flat`` / ``grad`` (>= numel, a multiple of 4; the slack stays 0)."""
+        return _rup(numel, 4)
 
     def _conv_entry(self, key, shape):
         """(cout, cin, ks, transposed, needs an input gradient) of the 4-d parameter ``key`` for the pack table, or
@@ -265,7 +272,7 @@ class Trainer:
             y_keep = b
         else:
             y_keep = None
-        if bn_stats and self.fuse_bn_stats and not nchw_out and y.c == y.ck:
+        if bn_stats and self.fuse_bn_stats and not nchw_out and (y.c == y.ck or self.bn_over_stored):
             # the BatchNorm that follows reads its statistics from the conv epilogue's partial sums
             rows = C.c_int(0)
             rc = L.udp_conv2d_fused_bn(C.byref(op), self._dt, x.n, x.buf.data_ptr(), wf.data_ptr(), bias,
@@ -321,7 +328,7 @@ class Trainer:
     def _bn(self, x, name, relu=True, res=None):
         L = _lib.lib()
         m, c = x.n * x.h * x.w, x.ck
-        if x.c != x.ck:
+        if x.c != x.ck and not self.bn_over_stored:
             raise ValueError("%s: BatchNorm over %d channels (not a multiple of 16)" % (name, x.c))
         y = self._new(x.n, x.h, x.w, x.c)
         save = torch.empty(2 * c, dtype=torch.float32, device=self.device)
@@ -401,6 +408,62 @@ class Trainer:
                     _lib.check(L.udp_upsample_bwd(g.data_ptr(), y.n, y.h, y.w, y.ck, s, t.grad.data_ptr(), int(have),
                                                   self._dt, self._stream()))
         self._tape.append((y, backward, None, []))
+        return y
+
+    def _maxpool(self, x):
+        """MaxPool2d(3, 2, 1) (pose_resnet.py:116, :199; shufflenetv2.py:124)."""
+        L = _lib.lib()
+        y = self._new(x.n, (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1, x.c)
+
+        _lib.check(L.udp_maxpool3s2_fwd(x.buf.data_ptr(), x.n, x.h, x.w, x.ck, self._dt, y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            if x.grad is not None:
+                raise RuntimeError("max-pool: its input has one consumer")
+            x.grad = self._like(x)
+            _lib.check(L.udp_maxpool3s2_bwd(x.buf.data_ptr(), y.grad.data_ptr(), x.n, x.h, x.w, x.ck, self._dt,
+                                            x.grad.data_ptr(), self._stream()))
+        self._tape.append((y, backward, None, []))
+        return y
+
+    def _deconv(self, x, name, bias_key=None):
+        """ConvTranspose2d(4, 2, 1) (pose_resnet.py:155-193): forward = the UDP_OP_DECONV kernel on the packed raw weights, weight
+        gradient = udp_conv2d_wgrad with ks 4 (dY as its `x`, the input as its `dy`), input gradient =
+        udp_deconv4s2_dgrad.  The head is a chain: the input has no other consumer."""
+        L = _lib.lib()
+        cout, cin, ks, wf, wd = self._convs[name]
+        if x.c != cin or x.c != x.ck:
+            raise ValueError("%s: expects %d input channels (a multiple of 16), got %d" % (name, cin, x.c))
+        y = self._new(x.n, 2 * x.h, 2 * x.w, cout)
+        op = self._conv_op(4, 2, x.ck, cout, x.h, x.w, y.h, y.w)
+        op.kind = _lib.UDP_OP_DECONV
+        bias, keep = self._zeros.data_ptr(), None
+        if bias_key:                                       # bias row padded to cout_pad
+            keep = torch.zeros(_rup(cout, 32), dtype=torch.float32, device=self.device)
+            keep[:cout] = self.param(bias_key)
+            bias = keep.data_ptr()
+        _lib.check(L.udp_conv2d_fused(C.byref(op), self._dt, x.n, x.buf.data_ptr(), wf.data_ptr(), bias, None, None, None,
+                                      None, y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            dy = y.grad                                    # NHWC [n,2h,2w,cout]
+
+            def wgrad():
+                _lib.check(L.udp_conv2d_wgrad(dy.data_ptr(), x.buf.data_ptr(), x.n, y.h, y.w, y.ck, x.h, x.w, x.ck, 4, 2,
+                                              cin, cout, self._dt, self._g(name + ".weight"), 0,
+                                              self._wgrad_ws.data_ptr(), self._wgrad_ws.numel(), self._stream()))
+                if bias_key:
+                    _lib.check(L.udp_bias_grad(dy.data_ptr(), y.n * y.h * y.w, y.ck, cout, self._g(bias_key), self._dt,
+                                               self._stream()))
+            self._on_side(wgrad, dy, x.buf)
+            if not x.needs_grad:
+                return
+            if x.grad is not None:
+                raise RuntimeError("%s: its input has one consumer" % name)
+            x.grad = self._like(x)
+            _lib.check(L.udp_deconv4s2_dgrad(dy.data_ptr(), wd.data_ptr(), x.n, x.h, x.w, cin, x.ck, cout, y.ck, self._dt,
+                                             x.grad.data_ptr(), self._stream()))
+        self._tape.append((y, backward, keep, [name + ".weight"] + ([bias_key] if bias_key else [])))
         return y
 
     def _backward_walk(self, dheat, pre=None):
@@ -992,62 +1055,6 @@ class PoseResNetTrainer(Trainer):
         self._tape.append((y, backward, None, ["conv1.weight"]))
         return y
 
-    def _maxpool(self, x):
-        """MaxPool2d(3, 2, 1) (:116, :199)."""
-        L = _lib.lib()
-        y = self._new(x.n, (x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1, x.c)
-
-        _lib.check(L.udp_maxpool3s2_fwd(x.buf.data_ptr(), x.n, x.h, x.w, x.ck, self._dt, y.buf.data_ptr(), self._stream()))
-
-        def backward():
-            if x.grad is not None:
-                raise RuntimeError("max-pool: its input has one consumer")
-            x.grad = self._like(x)
-            _lib.check(L.udp_maxpool3s2_bwd(x.buf.data_ptr(), y.grad.data_ptr(), x.n, x.h, x.w, x.ck, self._dt,
-                                            x.grad.data_ptr(), self._stream()))
-        self._tape.append((y, backward, None, []))
-        return y
-
-    def _deconv(self, x, name, bias_key=None):
-        """ConvTranspose2d(4, 2, 1) (:155-193): forward = the UDP_OP_DECONV kernel on the packed raw weights, weight
-        gradient = udp_conv2d_wgrad with ks 4 (dY as its `x`, the input as its `dy`), input gradient =
-        udp_deconv4s2_dgrad.  The head is a chain: the input has no other consumer."""
-        L = _lib.lib()
-        cout, cin, ks, wf, wd = self._convs[name]
-        if x.c != cin or x.c != x.ck:
-            raise ValueError("%s: expects %d input channels (a multiple of 16), got %d" % (name, cin, x.c))
-        y = self._new(x.n, 2 * x.h, 2 * x.w, cout)
-        op = self._conv_op(4, 2, x.ck, cout, x.h, x.w, y.h, y.w)
-        op.kind = _lib.UDP_OP_DECONV
-        bias, keep = self._zeros.data_ptr(), None
-        if bias_key:                                       # bias row padded to cout_pad
-            keep = torch.zeros(_rup(cout, 32), dtype=torch.float32, device=self.device)
-            keep[:cout] = self.param(bias_key)
-            bias = keep.data_ptr()
-        _lib.check(L.udp_conv2d_fused(C.byref(op), self._dt, x.n, x.buf.data_ptr(), wf.data_ptr(), bias, None, None, None,
-                                      None, y.buf.data_ptr(), self._stream()))
-
-        def backward():
-            dy = y.grad                                    # NHWC [n,2h,2w,cout]
-
-            def wgrad():
-                _lib.check(L.udp_conv2d_wgrad(dy.data_ptr(), x.buf.data_ptr(), x.n, y.h, y.w, y.ck, x.h, x.w, x.ck, 4, 2,
-                                              cin, cout, self._dt, self._g(name + ".weight"), 0,
-                                              self._wgrad_ws.data_ptr(), self._wgrad_ws.numel(), self._stream()))
-                if bias_key:
-                    _lib.check(L.udp_bias_grad(dy.data_ptr(), y.n * y.h * y.w, y.ck, cout, self._g(bias_key), self._dt,
-                                               self._stream()))
-            self._on_side(wgrad, dy, x.buf)
-            if not x.needs_grad:
-                return
-            if x.grad is not None:
-                raise RuntimeError("%s: its input has one consumer" % name)
-            x.grad = self._like(x)
-            _lib.check(L.udp_deconv4s2_dgrad(dy.data_ptr(), wd.data_ptr(), x.n, x.h, x.w, cin, x.ck, cout, y.ck, self._dt,
-                                             x.grad.data_ptr(), self._stream()))
-        self._tape.append((y, backward, keep, [name + ".weight"] + ([bias_key] if bias_key else [])))
-        return y
-
     # ------------------------------------------------------------------ the graph (pose_resnet.py:195-209)
     def _bottleneck(self, x, p, stride):
         """Bottleneck.forward (:82-100) as _make_layer builds it (:138-153): the stride sits on conv2 and on the 1x1
@@ -1081,3 +1088,241 @@ class PoseResNetTrainer(Trainer):
                          "deconv_layers.%d" % (3 * d + 1))
         self._out = self._conv(a, "final_layer", bias_key="final_layer.bias", nchw_out=True)
         return self._out.buf
+
+
+class ShuffleNetV2Trainer(Trainer):
+    """pose_shufflenetv2_10x_pixel_shuffle (deep_hrnet/lib/models/pose_shufflenetv2_10x_pixel_shuffle.py:23-53; recipe
+    experiments/coco/shufflenetv2/10x_256x192_adam_lr1e-3_pixel_shuffle.yaml) on the base step.  ``spec``: the dict of
+    ``shufflenet_plan.shufflenet_spec``.  fp32 only: the reference's precision, and the depthwise kernels have no bf16 form.
+
+    Channel counts here are not multiples of 16 (24, 58, 88, 116, 232 ...).  A tensor of c channels is stored with
+    ck = ceil16(c); every 1-d parameter (and running statistic) occupies ceil16(c) floats of ``flat`` / ``grad`` whose
+    slack is 0, and the BatchNorm kernels run over the ck stored channels (``bn_over_stored``).  That is exact as long as
+    every stored channel of every activation and gradient is written by its producer and the padded ones are exactly 0:
+    a padded channel then has mean 0, variance 0, gamma = beta = 0, output 0, gradient 0, and Adam leaves its slots at 0.
+
+    A unit's output stays a pair of halves (a, b) -- the concat (:92) is materialised only where a whole tensor is read
+    (a stride-2 unit, ``conv_last``); a stride-1 unit's channel_shuffle (:86-92) reads the pair directly."""
+
+    NAME = "pose_shufflenetv2_10x_pixel_shuffle"
+    bn_over_stored = True
+
+    def __init__(self, spec, num_joints, target_type, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-8, bucket_elems=6 * 1024 * 1024):
+        from .synth_shufflenet import shufflenet_units
+        if dtype != "f32":
+            raise ValueError("%s trains in fp32 only (dtype %r): the depthwise kernels have no bf16 form" % (self.NAME, dtype))
+        self.spec = dict(spec)
+        shapes = self._head_shapes(num_joints, target_type)
+        self._units = shufflenet_units(self.spec["model_size"])
+        super().__init__(shapes, state_dict, num_joints, target_type, device=device, dtype=dtype, lr=lr, betas=betas, eps=eps,
+                         bucket_elems=bucket_elems)
+        # one workspace for every depthwise weight gradient (they run in order on the side stream): the widest split
+        widest = max(_rup(s[0], 16) for k, s in shapes.items() if self._is_dw(k, s))
+        self._dw_ws = torch.empty(int(_lib.lib().udp_dwconv3_wgrad_workspace_bytes(256, 1, 1, widest)), dtype=torch.uint8,
+                                  device=self.device)
+
+    def _head_shapes(self, num_joints, target_type):
+        from .synth_shufflenet import shufflenet_param_shapes
+        sp = self.spec
+        if any(a % 64 for a in sp["architecture"]):
+            raise ValueError("%s trainer: ARCHITECTURE=%s -- the pixel shuffle moves 16 input channels per thread, every entry "
+                             "must be a multiple of 64" % (self.NAME, tuple(sp["architecture"])))
+        return shufflenet_param_shapes(model_size=sp["model_size"], num_joints=int(num_joints), target_type=target_type,
+                                       start_channels=sp["start_channels"], architecture=tuple(sp["architecture"]),
+                                       final_kernel=sp["final_kernel"])
+
+    @staticmethod
+    def _is_dw(key, shape):
+        return len(shape) == 4 and shape[1] == 1 and shape[2] == 3 and (".branch_main.3." in key or ".branch_proj.0." in key)
+
+    def _key_stride(self, key, numel):
+        return _rup(numel, 16 if len(self._shapes[key]) == 1 else 4)
+
+    def _conv_entry(self, key, shape):
+        if self._is_dw(key, shape):
+            return None                     # the depthwise kernels read the parameter as it is
+        if key.startswith("deconv_layers."):
+            return shape[1], shape[0], shape[2], True, True       # ConvTranspose2d.weight is [cin][cout][k][k]
+        return shape[0], shape[1], shape[2], False, key != "backbone.first_conv.0.weight"
+
+    # ------------------------------------------------------------------ the ops the other nets do not have
+    def _dw(self, x, name, stride):
+        """Depthwise 3x3 (shufflenetv2.py:54, :66) straight from the parameter; its input gradient accumulates when the
+        input already has one (the input of a stride-2 unit feeds both branches)."""
+        L = _lib.lib()
+        key = name + ".weight"
+        c_real = self._shapes[key][0]
+        if x.c != c_real:
+            raise ValueError("%s: expects %d channels, got %d" % (name, c_real, x.c))
+        y = self._new(x.n, (x.h - 1) // stride + 1, (x.w - 1) // stride + 1, x.c)
+        _lib.check(L.udp_dwconv3_train_fwd(x.buf.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, stride, self._dt,
+                                           y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            dy = y.grad
+            self._on_side(lambda: _lib.check(L.udp_dwconv3_wgrad(
+                x.buf.data_ptr(), dy.data_ptr(), x.n, x.h, x.w, x.ck, c_real, stride, self._dt, self._g(key),
+                self._dw_ws.data_ptr(), self._dw_ws.numel(), self._stream())), dy, x.buf)
+            if not x.needs_grad:
+                return
+            have = x.grad is not None
+            if not have:
+                x.grad = self._like(x)
+            _lib.check(L.udp_dwconv3_dgrad(dy.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, stride, int(have),
+                                           self._dt, x.grad.data_ptr(), self._stream()))
+        self._tape.append((y, backward, None, [key]))
+        return y
+
+    def _one_consumer(self, what, *xs):
+        if any(x.grad is not None for x in xs):
+            raise RuntimeError("%s: its inputs have one consumer" % what)
+
+    def _shuffle(self, a, b):
+        """channel_shuffle of cat(a, b) (:86-92): (even, odd) logical channels."""
+        L = _lib.lib()
+        if a.c != b.c or a.ck != b.ck:
+            raise ValueError("channel shuffle: halves of %d and %d channels" % (a.c, b.c))
+        m = a.n * a.h * a.w
+        even, odd = self._new(a.n, a.h, a.w, a.c), self._new(a.n, a.h, a.w, a.c)
+        _lib.check(L.udp_shuffle_pair_fwd(a.buf.data_ptr(), b.buf.data_ptr(), m, a.c, a.ck, even.ck, self._dt,
+                                          even.buf.data_ptr(), odd.buf.data_ptr(), self._stream()))
+
+        def backward():
+            self._one_consumer("channel shuffle", a, b)
+            for t in (even, odd):
+                if t.grad is None:
+                    t.grad = torch.zeros_like(t.buf)
+            a.grad, b.grad = self._like(a), self._like(b)
+            _lib.check(L.udp_shuffle_pair_bwd(even.grad.data_ptr(), odd.grad.data_ptr(), m, a.c, even.ck, a.ck, self._dt,
+                                              a.grad.data_ptr(), b.grad.data_ptr(), self._stream()))
+        self._tape.append((_Group([even, odd]), backward, None, []))
+        return even, odd
+
+    def _cat(self, a, b):
+        """torch.cat((a, b), 1) (:92) materialised."""
+        L = _lib.lib()
+        m = a.n * a.h * a.w
+        y = self._new(a.n, a.h, a.w, a.c + b.c)
+        _lib.check(L.udp_chan_cat2(a.buf.data_ptr(), a.ck, a.c, b.buf.data_ptr(), b.ck, b.c, m, y.ck, self._dt,
+                                   y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            self._one_consumer("concat", a, b)
+            a.grad, b.grad = self._like(a), self._like(b)
+            _lib.check(L.udp_chan_uncat2(y.grad.data_ptr(), y.ck, m, self._dt, a.grad.data_ptr(), a.ck, a.c,
+                                         b.grad.data_ptr(), b.ck, b.c, self._stream()))
+        self._tape.append((y, backward, None, []))
+        return y
+
+    def _split(self, y, ra, rb):
+        """(y[:, :ra], y[:, ra:ra+rb]) as a pair of halves."""
+        L = _lib.lib()
+        m = y.n * y.h * y.w
+        a, b = self._new(y.n, y.h, y.w, ra), self._new(y.n, y.h, y.w, rb)
+        _lib.check(L.udp_chan_uncat2(y.buf.data_ptr(), y.ck, m, self._dt, a.buf.data_ptr(), a.ck, ra, b.buf.data_ptr(),
+                                     b.ck, rb, self._stream()))
+
+        def backward():
+            self._one_consumer("split", y)
+            for t in (a, b):
+                if t.grad is None:
+                    t.grad = torch.zeros_like(t.buf)
+            y.grad = self._like(y)
+            _lib.check(L.udp_chan_cat2(a.grad.data_ptr(), a.ck, ra, b.grad.data_ptr(), b.ck, rb, m, y.ck, self._dt,
+                                       y.grad.data_ptr(), self._stream()))
+        self._tape.append((_Group([a, b]), backward, None, []))
+        return a, b
+
+    def _pixshuf(self, x):
+        """nn.PixelShuffle(2) (DUC.py:27)."""
+        L = _lib.lib()
+        if x.c != x.ck or x.c % 64:
+            raise ValueError("pixel shuffle over %d channels (a multiple of 64)" % x.c)
+        y = self._new(x.n, 2 * x.h, 2 * x.w, x.c // 4)
+        _lib.check(L.udp_pixshuf2_train_fwd(x.buf.data_ptr(), x.n, x.h, x.w, x.c, self._dt, y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            self._one_consumer("pixel shuffle", x)
+            x.grad = self._like(x)
+            _lib.check(L.udp_pixshuf2_train_bwd(y.grad.data_ptr(), x.n, x.h, x.w, x.c, self._dt, x.grad.data_ptr(),
+                                                self._stream()))
+        self._tape.append((y, backward, None, []))
+        return y
+
+    # ------------------------------------------------------------------ the graph (shufflenetv2.py:77-92, :154-158)
+    def _main(self, x, p, stride):
+        m = self._bn(self._conv(x, p + ".branch_main.0", bn_stats=True), p + ".branch_main.1")               # pw (:50-52)
+        m = self._bn(self._dw(m, p + ".branch_main.3", stride), p + ".branch_main.4", relu=False)            # dw (:54-55)
+        return self._bn(self._conv(m, p + ".branch_main.5", bn_stats=True), p + ".branch_main.6")            # pw (:57-59)
+
+    def _unit_s2(self, x, p):
+        proj = self._bn(self._dw(x, p + ".branch_proj.0", 2), p + ".branch_proj.1", relu=False)              # dw (:66-67)
+        proj = self._bn(self._conv(proj, p + ".branch_proj.2", bn_stats=True), p + ".branch_proj.3")         # pw (:69-71)
+        return proj, self._main(x, p, 2)
+
+    def _unit_s1(self, pair, p):
+        even, odd = self._shuffle(*pair)
+        return even, self._main(odd, p, 1)
+
+    def _head(self, a):
+        """PixelShuffleDecoder (decoders/pixelshuffle.py:29-33, DUC.py:23-28)."""
+        a = self._conv(a, "decoder.conv_compress")
+        for d in range(len(self.spec["architecture"])):
+            a = self._pixshuf(self._bn(self._conv(a, "decoder.duc.%d.conv" % d, bn_stats=True), "decoder.duc.%d.bn" % d))
+        return a
+
+    def forward(self, x):
+        """Train-mode forward.  x: fp32 [N,3,H,W] on the device.  Returns fp32 [N,C,H/4,W/4]."""
+        L = _lib.lib()
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+            raise ValueError("expected contiguous fp32 [N,3,H,W]")
+        n, _, h, w = x.shape
+        if h % 32 or w % 32:
+            raise ValueError("input %dx%d must be a multiple of 32" % (h, w))
+        self._tape = []
+        _lib.check(L.udp_pack_conv_weights_batch(self._pack_table.data_ptr(), len(self._convs), self._dt, self._stream()))
+        a = self._new(n, h, w, 3, needs_grad=False)
+        _lib.check(L.udp_nchw_to_nhwc(x.data_ptr(), n, 3, h, w, a.ck, a.buf.data_ptr(), self._dt, self._stream()))
+        a = self._bn(self._conv(a, "backbone.first_conv.0", stride=2, bn_stats=True), "backbone.first_conv.1")   # :118-122
+        a = self._maxpool(a)                                                                                     # :124
+        pair = None
+        for idx, inp, oup, mid, stride in self._units:
+            p = "backbone.features.%d" % idx
+            if stride == 2:
+                if pair is not None:
+                    a = self._cat(*pair)
+                pair = self._unit_s2(a, p)
+                if pair[0].c != pair[1].c:         # the first unit: inp and oup - inp channels; the shuffle wants halves
+                    half = (pair[0].c + pair[1].c) // 2
+                    pair = self._split(self._cat(*pair), half, half)
+            else:
+                pair = self._unit_s1(pair, p)
+        a = self._cat(*pair)
+        a = self._bn(self._conv(a, "backbone.conv_last.0", bn_stats=True), "backbone.conv_last.1")               # :143-147
+        a = self._head(a)
+        self._out = self._conv(a, "final_layer", bias_key="final_layer.bias", nchw_out=True)
+        return self._out.buf
+
+
+class ShuffleNetV2DeconvTrainer(ShuffleNetV2Trainer):
+    """pose_shufflenetv2_10x (pose_shufflenetv2_10x.py:22-97; recipe experiments/coco/shufflenetv2/10x_256x192_adam_lr1e-3.yaml):
+    the same backbone, the deconv head of pose_resnet behind ``conv_last``.  ``spec``: ``shufflenet_plan.shufflenet_deconv_spec``."""
+
+    NAME = "pose_shufflenetv2_10x"
+
+    def _head_shapes(self, num_joints, target_type):
+        from .synth_shufflenet import shufflenet_deconv_param_shapes
+        sp = self.spec
+        if any(f % 16 for f in sp["deconv_filters"]):
+            raise ValueError("%s trainer: deconv filters in multiples of 16 (got %s)" % (self.NAME, tuple(sp["deconv_filters"])))
+        return shufflenet_deconv_param_shapes(model_size=sp["model_size"], num_joints=int(num_joints), target_type=target_type,
+                                              deconv_filters=tuple(sp["deconv_filters"]), final_kernel=sp["final_kernel"],
+                                              deconv_with_bias=sp["deconv_with_bias"])
+
+    def _head(self, a):
+        for d in range(len(self.spec["deconv_filters"])):
+            q = "deconv_layers.%d" % (3 * d)
+            a = self._bn(self._deconv(a, q, q + ".bias" if self.spec["deconv_with_bias"] else None),
+                         "deconv_layers.%d" % (3 * d + 1))
+        return a
