@@ -10,6 +10,7 @@ namespace udp {
 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -188,6 +189,78 @@ __device__ __forceinline__ void h2_add8(f32x4& a, f32x4& b, const f16x8 hi, cons
   }
 }
 
+// ---- The same arithmetic in fewer instructions (the epilogue of the weight-stationary kernels, conv_ws.hip UDP_WS_FAST_EPI).
+// Every IEEE operation of h2_add8 / h2_split8 / the ReLU and its rounding stays; what goes is the instructions around them:
+// v_fma_mix_f32 reads an fp16 half of a register as an fma operand (exact widening, fp16 denormals kept: the kernels run
+// with both denormal modes on), so the separate v_cvt_f32_f16 of every residual element and of every stored hi value
+// disappear.  Inline assembly because hipcc widens first and then packs the fp32 work into pairs.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+// (float)hi.half[H] + (float)lo.half[H] * 2^-11 as ONE fma -- what hipcc contracts h2_add8's expression to (the product is
+// exact either way: a power of two, no underflow in fp32)
+template <int H>
+__device__ __forceinline__ float h2_join_mix(unsigned hi, unsigned lo) {
+  float r;
+  if constexpr (H == 0)
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(lo), "v"(kLoInv), "v"(hi));
+  else
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(lo), "v"(kLoInv), "v"(hi));
+  return r;
+}
+// v - (float)h.half[H]: fma(h, -1, v), the same single rounding as the subtraction
+template <int H>
+__device__ __forceinline__ float h2_sub_mix(float v, unsigned h) {
+  float r;
+  if constexpr (H == 0)
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(-1.f), "v"(v));
+  else
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(-1.f), "v"(v));
+  return r;
+}
+// h2_add8 on the raw registers of the residual (hi / lo: 8 fp16 values each)
+__device__ __forceinline__ void h2_add8_fast(f32x4& a, f32x4& b, const u32x4 hi, const u32x4 lo) {
+  a[0] += h2_join_mix<0>(hi[0], lo[0]);
+  a[1] += h2_join_mix<1>(hi[0], lo[0]);
+  a[2] += h2_join_mix<0>(hi[1], lo[1]);
+  a[3] += h2_join_mix<1>(hi[1], lo[1]);
+  b[0] += h2_join_mix<0>(hi[2], lo[2]);
+  b[1] += h2_join_mix<1>(hi[2], lo[2]);
+  b[2] += h2_join_mix<0>(hi[3], lo[3]);
+  b[3] += h2_join_mix<1>(hi[3], lo[3]);
+}
+// ReLU as the one v_max_f32 lim, v that hipcc emits for `v > 0 ? v : 0` (lim = 0), without the canonicalising
+// v_max_f32 v, v it puts in front when the value comes from another basic block.  The operands here are results of fp32
+// additions -- never a signalling NaN -- so the instruction sees what it saw before: NaN -> 0, -0 -> +0.  lim = a quiet
+// NaN is "no ReLU": v_max_f32 returns the other operand whatever it is (a NaN too, bit for bit), so the caller needs no branch.
+__device__ __forceinline__ void relu8_fast(f32x4& a, f32x4& b, float lim) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    asm("v_max_f32 %0, %1, %2" : "=v"(a[q]) : "v"(lim), "v"(a[q]));
+    asm("v_max_f32 %0, %1, %2" : "=v"(b[q]) : "v"(lim), "v"(b[q]));
+  }
+}
+// the largest h2_mag() of m and eight more values in four v_max3_u32.  NONNEG: the values
+// come out of relu8_fast (+0 .. +inf, no NaN, no -0), so their bit patterns are their magnitudes
+template <bool NONNEG>
+__device__ __forceinline__ unsigned h2_mag8(unsigned m, const f32x4& a, const f32x4& b) {
+  auto mg = [](float v) { return NONNEG ? __builtin_bit_cast(unsigned, v) : h2_mag(v); };
+  m = h2_max(h2_max(m, mg(a[0])), mg(a[1]));
+  m = h2_max(h2_max(m, mg(a[2])), mg(a[3]));
+  m = h2_max(h2_max(m, mg(b[0])), mg(b[1]));
+  m = h2_max(h2_max(m, mg(b[2])), mg(b[3]));
+  return m;
+}
+// h2_split8 without its range check (the caller keeps h2_mag8 and checks once): packed round-to-nearest converts
+__device__ __forceinline__ void h2_split8_fast(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
+  const f32x2 v[4] = {{a[0], a[1]}, {a[2], a[3]}, {b[0], b[1]}, {b[2], b[3]}};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(v[k], f16x2));
+    const f32x2 d = {h2_sub_mix<0>(v[k][0], h), h2_sub_mix<1>(v[k][1], h)};
+    hi[k] = h;
+    lo[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(d * kLoScale, f16x2));
+  }
+}
+
 // 4*NB consecutive channels <-> NB accumulator tiles of one lane.  `p` points at the lane's first
 // channel (bytes); H2: the lo plane starts lo_off bytes further
 template <typename T, int NB>
@@ -212,7 +285,6 @@ __device__ __forceinline__ void add_vec(f32x4 (&v)[NB], const unsigned char* p, 
   }
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned kOobOff = 0x7FFF0000u;   // voffset of a masked lane: beyond every buffer (< 2 GiB), no wrap with + small
 
 // x / d for x*d < 2^20 with m = ceil(2^20 / d): one full-rate 24-bit multiply and a shift

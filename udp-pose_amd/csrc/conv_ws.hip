@@ -23,6 +23,24 @@ namespace udp {
 #ifndef UDP_WS_LATE_RES
 #define UDP_WS_LATE_RES 1
 #endif
+// UDP_WS_FAST_EPI / UDP_WS_FAST_ADDR (compile time, default 1; 0 = the earlier code, for A/B builds): the
+// same values from fewer vector-ALU instructions -- the ALU shares the SIMD with the MFMAs, and the counters show the two
+// mostly adding up (NOTES).
+//   FAST_EPI   the epilogue: residual decode and hi/lo split through the mixed-precision fma and the packed round-to-nearest
+//              fp32 -> fp16 convert (h2_add8_fast / h2_split8_fast, conv_dev.h), the range check as one max3 chain and
+//              one compare per pixel block
+//   FAST_ADDR  the B-fragment LDS address: byte row offsets kept per block (kg's 16-byte part folded in), stage base + tap
+//              offset as one wave-uniform term, the swizzle bit taken from the byte address
+#ifndef UDP_WS_FAST_EPI
+#define UDP_WS_FAST_EPI 1
+#endif
+#ifndef UDP_WS_FAST_ADDR
+#define UDP_WS_FAST_ADDR 1
+#endif
+#ifdef UDP_OLD_SWZ      // (the address form below spells out the current swizzle)
+#undef UDP_WS_FAST_ADDR
+#define UDP_WS_FAST_ADDR 0
+#endif
 // residual of one pixel block (8 consecutive split-fp16 channels per lane), raw until the epilogue adds it
 template <int NB>
 struct ResH2 {
@@ -39,7 +57,13 @@ __device__ __forceinline__ void load_res_h2(ResH2<NB>& o, __amdgpu_buffer_rsrc_t
 template <int NB>
 __device__ __forceinline__ void add_res_h2(f32x4 (&v)[NB], const ResH2<NB>& o) {
 #pragma unroll
-  for (int h = 0; h < NB / 2; ++h) h2_add8(v[2 * h], v[2 * h + 1], __builtin_bit_cast(f16x8, o.hi[h]), __builtin_bit_cast(f16x8, o.lo[h]));
+  for (int h = 0; h < NB / 2; ++h) {
+#if UDP_WS_FAST_EPI
+    h2_add8_fast(v[2 * h], v[2 * h + 1], o.hi[h], o.lo[h]);
+#else
+    h2_add8(v[2 * h], v[2 * h + 1], __builtin_bit_cast(f16x8, o.hi[h]), __builtin_bit_cast(f16x8, o.lo[h]));
+#endif
+  }
 }
 
 // HS: the hard-swish / SiLU instantiations (HS = udp_conv_op.relu = UDP_ACT_HSWISH | UDP_ACT_SILU; conv_ws_hs_kernel below)
@@ -191,6 +215,9 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
     const int r = fdiv20(rem, p.mTW);
     const int x = rem - (int)__umul24(r, p.TW);
     prow[i] = (int)__umul24(__umul24(g, IH) + r * STRIDE, IW) + x * STRIDE;
+#if UDP_WS_FAST_ADDR
+    prow[i] = prow[i] * ROWB + (kg << 4);      // byte offset of the row in a plane, the lane's unswizzled part in bits 4..5
+#endif
     const int n = n0 + g, y = y0 + r, xo = x0 + x;
     const bool ok = m0 < M && n < p.N && y < p.Hout && xo < p.Wout && (NCHW || cbase < p.Cout);
     const unsigned pix = __umul24(__umul24(n, p.Hout) + y, p.Wout) + xo;
@@ -305,12 +332,25 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
     // B fragments (hi, lo) in a ring of three: the LDS reads of block i + 2 are issued before the MFMAs of
     // block i (one wave per SIMD has nothing else to cover the ~200-cycle LDS latency with)
     f16x8 xh[3], xl[3];
+#if UDP_WS_FAST_ADDR
+    // stage base + tap offset: one wave-uniform byte offset per step (a stage is a multiple of 2 KiB, so bits 6.. of the
+    // sum are still the row's: swz<H2>(row) = bit 2 of the row = bit 8 of the byte offset, applied to bit 5 = part bit 1)
+    const unsigned tap_off = (unsigned)(sb - smem) + (unsigned)tap_rows * ROWB;
+    auto load_b = [&](int i, f16x8& h, f16x8& l) __attribute__((always_inline)) {
+      const unsigned rb = (unsigned)prow[i] + tap_off;
+      // rb ^ ((rb >> 3) & 32) as shift + one three-input bit operation (table 0x6c = (a & c) ^ b)
+      const unsigned char* q = smem + __builtin_amdgcn_bitop3_b32(rb >> 3, rb, 32u, 0x6c);
+      h = *reinterpret_cast<const f16x8*>(q);
+      l = *reinterpret_cast<const f16x8*>(q + in_bytes);
+    };
+#else
     auto load_b = [&](int i, f16x8& h, f16x8& l) __attribute__((always_inline)) {
       const int row = prow[i] + tap_rows;
       const unsigned char* q = sb + row * ROWB + ((kg ^ swz<T>(row)) << 4);
       h = *reinterpret_cast<const f16x8*>(q);
       l = *reinterpret_cast<const f16x8*>(q + in_bytes);
     };
+#endif
     load_b(0, xh[0], xl[0]);
     if (PB > 1) load_b(1, xh[1], xl[1]);
 #pragma unroll
@@ -370,6 +410,9 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   }
 
   // ---- epilogue: lane holds couts cbase .. cbase + 7 of pixel i
+#if UDP_WS_FAST_EPI
+  [[maybe_unused]] const float relu_lim = p.relu ? 0.f : __builtin_nanf("");
+#endif
 #pragma unroll
   for (int i = 0; i < PB; ++i) {
     f32x4 v[NB];
@@ -406,6 +449,28 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
           }
         }
       }
+#if UDP_WS_FAST_EPI
+      // the range check follows the activation as before (h2_split8): one max3 chain and one compare per block
+      unsigned mag;
+      if constexpr (HS) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[nb][q] = act_hs<HS>(v[nb][q]);
+        mag = h2_mag8<false>(0u, v[0], v[1]);
+      } else {
+        // ReLU without a branch around it (relu_lim: 0, or a NaN that lets every value through), so that the blocks' code
+        // does not have to meet again behind one; only the maximum for the range check still depends on which it was
+        relu8_fast(v[0], v[1], relu_lim);
+        mag = p.relu ? h2_mag8<true>(0u, v[0], v[1]) : h2_mag8<false>(0u, v[0], v[1]);
+      }
+      // (one check per block, not one per wave: with the blocks' code free to mix, conv_ws_multi<1> spills two more SGPRs)
+      h2_range_check_bits(mag);
+      u32x4 shi, slo;
+      h2_split8_fast(v[0], v[1], shi, slo);
+      __builtin_amdgcn_raw_buffer_store_b128(shi, r_out, ooff, 0, UDP_H2_STORE_AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(slo, r_out, ooff + out_lo, 0, UDP_H2_STORE_AUX);
+#else
       if constexpr (HS) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
@@ -419,6 +484,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
           for (int q = 0; q < 4; ++q) v[nb][q] = v[nb][q] > 0.f ? v[nb][q] : 0.f;
       }
       store_vec_buf<T, NB>(r_out, ooff, out_lo, v);
+#endif
       // (only in the kernels of convs launched on their own: with this code the merged kernel spills 4 KB per lane)
       if (OUT2 && p.nout2) {   // wave-uniform, rare (RSN bottleneck): out2_k = out AS STORED + add2_k (udp_conv_op.n_out2)
         f16x8 sh, sl;
