@@ -41,6 +41,18 @@ namespace udp {
 #undef UDP_WS_FAST_ADDR
 #define UDP_WS_FAST_ADDR 0
 #endif
+// UDP_WS_INC_STEP (compile time, default 1; 0 = the earlier code, for A/B builds): the step decode of the 3x3 stride-1 bodies
+// (LATE below) without divisions.  A trip of their loop is one tap row, so tap % 3 is the compile-time ring slot, and
+// tap / 3, the chunk, the row's byte offset and the scalar offset of the next A fragments are running values; the LDS base is
+// part of the wave-uniform tap offset, so the B address loses the add of the (zero) base symbol that hipcc does not fold.
+// Same MFMAs, same operands, same order (NOTES, r11: of three parts measured, the one that pulled on its own).
+#ifndef UDP_WS_INC_STEP
+#define UDP_WS_INC_STEP 1
+#endif
+#if !UDP_WS_FAST_ADDR      // (it builds on the FAST_ADDR address form)
+#undef UDP_WS_INC_STEP
+#define UDP_WS_INC_STEP 0
+#endif
 // residual of one pixel block (8 consecutive split-fp16 channels per lane), raw until the epilogue adds it
 template <int NB>
 struct ResH2 {
@@ -74,7 +86,8 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   using T = H2;
   constexpr int CK = 32, ESZ = 2, NB = 2, NW = 4;
   constexpr int PAD = KS / 2, TAPS = KS * KS;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // (INC_STEP adds the LDS base to the row offset in front of the swizzle, which looks at bit 8: a base aligned to 512)
+  extern __shared__ __attribute__((aligned(UDP_WS_INC_STEP ? 512 : 16))) unsigned char smem[];
 
   UDP_STAMP(0);
   const int tid = threadIdx.x;
@@ -143,14 +156,16 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   constexpr int AD = UDP_WS_AD;          // depth of the A ring (fragments of step s + AD - 1 are in flight)
   f16x8 ah[AD][NB], al[AD][NB];
   const int nsteps = nchunks * TAPS;
-  auto load_a = [&](int s, f16x8 (&h)[NB], f16x8 (&l)[NB]) __attribute__((always_inline)) {
-    const int c = s / TAPS, tap = s - c * TAPS;
-    const unsigned soff = (unsigned)(tap * nchunks + c) * (npairs * 4096u) + wpair;
+  auto load_a_at = [&](unsigned soff, f16x8 (&h)[NB], f16x8 (&l)[NB]) __attribute__((always_inline)) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       h[nb] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_w, wvoff + 2048u * nb, soff, 0));
       l[nb] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_w, wvoff + 2048u * nb + 1024u, soff, 0));
     }
+  };
+  auto load_a = [&](int s, f16x8 (&h)[NB], f16x8 (&l)[NB]) __attribute__((always_inline)) {
+    const int c = s / TAPS, tap = s - c * TAPS;
+    load_a_at((unsigned)(tap * nchunks + c) * (npairs * 4096u) + wpair, h, l);
   };
 
   // The prologue issues every load it can before it waits for any: A fragments of steps 0 and 1 and the bias first
@@ -270,6 +285,16 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
   UDP_STAMP(2);
   int c = 0, tap = 0;                     // chunk / tap of the current step
   const unsigned char* sb = smem;
+  // INC_STEP: the same as running values -- the tap row dy = tap / 3 and its byte offset dy * IW * ROWB advance once per trip
+  // of the LATE loop, the scalar offset of the A fragments to request next once per step, the stage's LDS address per chunk
+  constexpr bool INC = UDP_WS_INC_STEP && LATE;
+  using lds_u8 = const __attribute__((address_space(3))) unsigned char*;
+  using lds_f16x8 = const __attribute__((address_space(3))) f16x8*;
+  [[maybe_unused]] const unsigned lds0 = INC ? (unsigned)(size_t)(lds_u8)smem : 0u;
+  [[maybe_unused]] const unsigned a_tap = (unsigned)nchunks * (npairs * 4096u);      // from one tap to the next of a chunk
+  [[maybe_unused]] unsigned a_next = (unsigned)(AD - 1) * a_tap + wpair;             // (the prologue fetched steps 0 .. AD - 2)
+  [[maybe_unused]] int dy = 0;
+  [[maybe_unused]] unsigned row_off = 0, sb_off = lds0;
   // TAIL: -1 inside the step loop; 0, 1, 2 = taps 6, 7, 8 of the last chunk in the peeled tail (LATE only)
   auto step = [&](auto BUFC, auto TAILC, int s) __attribute__((always_inline)) {
     constexpr int BUF = decltype(BUFC)::value, TAIL = decltype(TAILC)::value;
@@ -281,12 +306,19 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
 #if !(UDP_WS_DBG & 1)
     if constexpr (!LATE)
       load_a(s + AD - 1 < nsteps ? s + AD - 1 : nsteps - 1, ah[(BUF + AD - 1) % AD], al[(BUF + AD - 1) % AD]);
-    else if constexpr (TAIL <= 0)
-      load_a(s + AD - 1, ah[(BUF + AD - 1) % AD], al[(BUF + AD - 1) % AD]);
+    else if constexpr (TAIL <= 0) {
+      if constexpr (INC) {
+        // (tap BUF + 2 of this row; behind tap 2 of the last row comes tap 0 of the next chunk)
+        load_a_at(a_next, ah[(BUF + AD - 1) % AD], al[(BUF + AD - 1) % AD]);
+        a_next += (BUF == 0 && dy == KS - 1) ? npairs * 4096u - (unsigned)(TAPS - 1) * a_tap : a_tap;
+      } else {
+        load_a(s + AD - 1, ah[(BUF + AD - 1) % AD], al[(BUF + AD - 1) % AD]);
+      }
+    }
 #endif
     if constexpr (TAIL == 0) load_res(std::integral_constant<int, 0>{}, std::integral_constant<int, RSPLIT>{});
     if constexpr (TAIL == 1 && RSPLIT < PB) load_res(std::integral_constant<int, RSPLIT>{}, std::integral_constant<int, PB>{});
-    if (TAIL < 0 && tap == 0) {
+    if (TAIL < 0 && (INC ? BUF == 0 && dy == 0 : tap == 0)) {
       // chunk c's DMA has landed (vector-memory operations complete in issue order: all but the 2*NB A loads
       // just issued, which may stay in flight; letting the previous step's stay in flight too changes nothing)
       if (c == 1) UDP_STAMP(9);                           // (diagnostic builds only: chunk-boundary stamps of chunks 1, 2, 4)
@@ -305,6 +337,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         sb = smem;
+        if constexpr (INC) sb_off = lds0;
       } else {
         if (s == 0)
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NB + (LATE ? 0 : NR)) : "memory");
@@ -320,6 +353,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
         if (c + 1 < nchunks && !((STRIDE == 2 || OUT2) && p.sbuf)) stage(c + 1, smem + ((c + 1) & 1) * stage_bytes);
 #endif
         sb = smem + (c & 1) * stage_bytes;
+        if constexpr (INC) sb_off = lds0 + (unsigned)((c & 1) * stage_bytes);
       }
     }
     // the cross term hi * Xlo: activations keep their lo plane scaled by 2^11 (storage format), so the weight side
@@ -335,13 +369,21 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
 #if UDP_WS_FAST_ADDR
     // stage base + tap offset: one wave-uniform byte offset per step (a stage is a multiple of 2 KiB, so bits 6.. of the
     // sum are still the row's: swz<H2>(row) = bit 2 of the row = bit 8 of the byte offset, applied to bit 5 = part bit 1)
-    const unsigned tap_off = (unsigned)(sb - smem) + (unsigned)tap_rows * ROWB;
+    // (INC_STEP: the stage's LDS address + the row's running offset + the tap's place in the row; in the tail BUF = TAIL and
+    // row_off stands at the last row)
+    const unsigned tap_off = INC ? sb_off + row_off + (unsigned)(BUF * ROWB) : (unsigned)(sb - smem) + (unsigned)tap_rows * ROWB;
     auto load_b = [&](int i, f16x8& h, f16x8& l) __attribute__((always_inline)) {
       const unsigned rb = (unsigned)prow[i] + tap_off;
       // rb ^ ((rb >> 3) & 32) as shift + one three-input bit operation (table 0x6c = (a & c) ^ b)
-      const unsigned char* q = smem + __builtin_amdgcn_bitop3_b32(rb >> 3, rb, 32u, 0x6c);
-      h = *reinterpret_cast<const f16x8*>(q);
-      l = *reinterpret_cast<const f16x8*>(q + in_bytes);
+      const unsigned a = __builtin_amdgcn_bitop3_b32(rb >> 3, rb, 32u, 0x6c);
+      if constexpr (INC) {      // `a` is the LDS address itself
+        h = *reinterpret_cast<lds_f16x8>((size_t)a);
+        l = *reinterpret_cast<lds_f16x8>((size_t)(a + (unsigned)in_bytes));
+      } else {
+        const unsigned char* q = smem + a;
+        h = *reinterpret_cast<const f16x8*>(q);
+        l = *reinterpret_cast<const f16x8*>(q + in_bytes);
+      }
     };
 #else
     auto load_b = [&](int i, f16x8& h, f16x8& l) __attribute__((always_inline)) {
@@ -371,7 +413,17 @@ __device__ __forceinline__ void conv_ws_body(const ConvParams& p, const int tile
 #endif
     }
     if constexpr (TAIL < 0) {
-      if (++tap == TAPS) {
+      if constexpr (INC) {
+        if constexpr (BUF == KS - 1) {      // the row is done
+          ++dy;
+          row_off += (unsigned)IW * ROWB;
+          if (dy == KS) {
+            dy = 0;
+            row_off = 0;
+            ++c;
+          }
+        }
+      } else if (++tap == TAPS) {
         tap = 0;
         ++c;
       }
