@@ -870,6 +870,70 @@ int udp_chan_uncat2(const void* y, int c, int64_t m, int dtype, void* a, int pa,
                     void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Training of the MobileNetV3-small pose nets (pose_mobilenetv3_small_pixel_shuffle,
+ * pose_mobilenetv3_small; recipes experiments/coco/mobilenetv3/): what their
+ * backbone -- torchvision's mobilenet_v3_small().features,
+ * deep_hrnet/lib/models/backbones/mobilenetv3.py:5-16; the block table is
+ * udp_pose_amd/synth_mobilenetv3.py BLOCKS -- adds to a ShuffleNetV2 step
+ * (csrc/mobilenetv3_train.hip).  fp32 only (UDP_F32; anything else is
+ * UDP_ERR_UNSUPPORTED).  Symbols only: UDP_POSE_ABI_VERSION stays as it is.
+ *
+ * The conventions of the section above hold: NHWC tensors with a stored channel count c % 4 == 0, c_real <= c real
+ * channels first; every stored channel of every output is written and the padded ones are exact zeros; no atomics, one
+ * summation order per shape (two runs, and eager and captured steps, are bit-equal); no host synchronisation and no
+ * allocation (capturable in a hipGraph); every argument check comes before anything touches the device.
+ * ------------------------------------------------------------------------- */
+/* Depthwise ks x ks conv (ks = 3 | 5), stride 1 | 2, padding ks/2, no bias, no activation (the depthwise member of an
+ * InvertedResidual under model.train(); BLOCKS columns `kernel`, `stride`): the contract of udp_dwconv3_train_fwd with
+ * a kernel size --
+ *   y[n,oy,ox,ch] = sum_{ky,kx} x[n, oy*s+ky-ks/2, ox*s+kx-ks/2, ch] * w[ch][0][ky][kx]
+ * as fmaf in (ky, kx) order with the taps outside the image skipped.  w: the parameter itself, [c_real][1][ks][ks]
+ * fp32, read in place, 16-byte aligned.  A thread owns a strip of consecutive output pixels of one row (2 for 3x3, 4
+ * for 5x5) x 4 channels and loads each input column of a kernel row once for the whole strip.  ks other than 3 | 5,
+ * stride other than 1 | 2: UDP_ERR_UNSUPPORTED. */
+int udp_dwconvk_train_fwd(const void* x, const void* w, int n, int hin, int win, int c, int c_real, int ks, int stride,
+                          int dtype, void* y, void* stream);
+/* Its input gradient, a gather like udp_dwconv3_dgrad:
+ *   dx[n,iy,ix,ch] (+)= sum_{ky,kx} dy[n, (iy+ks/2-ky)/s, (ix+ks/2-kx)/s, ch] * w[ch][ky][kx]
+ * over the taps where both divisions are exact and the index lies inside dy [n,hout,wout,c]; (ky, kx) order from 0,
+ * `accumulate` != 0 adds the sum to dx last. */
+int udp_dwconvk_dgrad(const void* dy, const void* w, int n, int hin, int win, int c, int c_real, int ks, int stride,
+                      int accumulate, int dtype, void* dx, void* stream);
+/* Its weight gradient in the parameter layout [c_real][1][ks][ks] (overwritten), with the fixed row split of
+ * udp_dwconv3_wgrad: partials = min(n*hout, 256, workspace_bytes / (4 ks^2 c)), rows = ceil(n*hout / partials),
+ * partials = ceil(n*hout / rows); [ks^2][c] partials in the workspace, added in index order by a second launch.  A
+ * workspace that holds no partial: UDP_ERR_WORKSPACE.  udp_dwconvk_wgrad_workspace_bytes: what the unconstrained split
+ * needs (0: bad shape or ks), never more than 256 * 4 ks^2 c bytes, which (n = 256, hout = 1) returns. */
+size_t udp_dwconvk_wgrad_workspace_bytes(int n, int hout, int wout, int c, int ks);
+int udp_dwconvk_wgrad(const void* x, const void* dy, int n, int hin, int win, int c, int c_real, int ks, int stride, int dtype,
+                      void* dw, void* workspace, size_t workspace_bytes, void* stream);
+/* nn.Hardswish (BLOCKS column `activation` = "HS", and behind the stem and the last conv) over `count` fp32 values,
+ * count a positive multiple of 4:  y = x * clamp(x + 3, 0, 6) / 6;
+ *   dx = 0 (x < -3) | dy * (x / 3 + 0.5) (-3 <= x <= 3) | dy (x > 3)      (x: the forward's INPUT).
+ * That is autograd's derivative of the clamp form.  At exactly x = -3 and x = 3 it differs from torch's
+ * hardswish_backward (nn.Hardswish, the reference backbone's layer), which takes the outer pieces there: 0 and dy
+ * instead of -0.5 dy and 1.5 dy.  Everywhere else the two are the same function.
+ * A BatchNorm with relu = 0 followed by this launch is BatchNorm + Hardswish; 0 maps to 0, so pads stay zero. */
+int udp_hswish_fwd(const void* x, void* y, int64_t count, void* stream);
+int udp_hswish_bwd(const void* dy, const void* x, void* dx, int64_t count, void* stream);
+/* torchvision.ops.SqueezeExcitation under model.train() (BLOCKS column `squeeze-excitation`; restated in
+ * tests/mobilenetv3_ref.py:squeeze_excitation):  y = x * hardsigmoid(W2 relu(W1 mean_hw(x) + b1) + b2)  per image.
+ * x, y: [n,h,w,c]; w1 = fc1.weight [sq][c_real][1][1], b1 [sq], w2 = fc2.weight [c_real][sq][1][1], b2 [c_real], fp32,
+ * read as they are.  Kept for the backward: pool [n][c] = mean_hw(x) (fp32, pixels added in a fixed order), hid [n][sq]
+ * after the ReLU, s [n][c] the gate pre-activation (pads of pool and s: 0).  Four launches: pool, fc1, fc2, scale. */
+int udp_se_train_fwd(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, int n, int h, int w,
+                     int c, int c_real, int sq, int dtype, float* pool, float* hid, float* s, void* y, void* stream);
+/* Its backward.  A map pass reduces dgate[n][ch] = sum_hw dy * x and leaves ds = dgate / 6 where -3 <= s <= 3, else 0;
+ * on the [n][.] rows: dh = (ds W2) (hid > 0), dpool = dh W1, and dW2 = ds^T hid, db2 = sum_n ds, dW1 = dh^T pool,
+ * db1 = sum_n dh (parameter layouts, overwritten, images in index order); a second map pass writes
+ * dx (+)= dy * hardsigmoid(s) + dpool / (h w).  workspace: udp_se_train_workspace_bytes(n, c, sq) bytes (0: bad shape);
+ * less is UDP_ERR_WORKSPACE. */
+size_t udp_se_train_workspace_bytes(int n, int c, int sq);
+int udp_se_train_bwd(const void* dy, const void* x, const float* w1, const float* w2, const float* pool, const float* hid,
+                     const float* s, int n, int h, int w, int c, int c_real, int sq, int accumulate, int dtype, void* dx,
+                     float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Training of the polarized self-attention block of pose_hrnet_psa.  Replaces
  * PSA_s.forward (deep_hrnet/lib/models/PSA.py:190-269: spatial_pool :190-222,
  * channel_pool :224-258) under model.train() and its autograd backward.

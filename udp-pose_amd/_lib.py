@@ -176,6 +176,17 @@ _SIGS = {
     "udp_shuffle_pair_bwd": (C.c_int, [_P, _P, C.c_int64] + [C.c_int] * 4 + [_P, _P, _P]),
     "udp_chan_cat2": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "udp_chan_uncat2": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    # training of the MobileNetV3-small pose nets: depthwise 3x3 | 5x5 forward / dgrad / wgrad, hard-swish, squeeze-and-
+    # excitation with biases (csrc/mobilenetv3_train.hip)
+    "udp_dwconvk_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P]),
+    "udp_dwconvk_dgrad": (C.c_int, [_P, _P] + [C.c_int] * 9 + [_P, _P]),
+    "udp_dwconvk_wgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "udp_dwconvk_wgrad": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P, C.c_size_t, _P]),
+    "udp_hswish_fwd": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "udp_hswish_bwd": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "udp_se_train_fwd": (C.c_int, [_P] * 5 + [C.c_int] * 7 + [_P] * 5),
+    "udp_se_train_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "udp_se_train_bwd": (C.c_int, [_P] * 7 + [C.c_int] * 8 + [_P] * 6 + [C.c_size_t, _P]),
     # training of the polarized self-attention block (pose_hrnet_psa)
     "udp_psa_train_save_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "udp_psa_train_fwd_pool": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),

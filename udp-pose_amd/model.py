@@ -69,8 +69,8 @@ class PoseNetHip:
         return dict(self._sd or {})
 
     def trainer(self):
-        raise NotImplementedError("%s: the training step covers pose_hrnet, pose_hrnet_psa, pose_resnet and the two "
-                                  "ShuffleNetV2 nets only" % self.NAME)
+        raise NotImplementedError("%s: the training step covers pose_hrnet, pose_hrnet_psa, pose_resnet, the two "
+                                  "ShuffleNetV2 nets and the two MobileNetV3-small nets only" % self.NAME)
 
     def to(self, device):
         self.device = torch.device(device)
@@ -836,17 +836,22 @@ def get_pose_net_shufflenetv2_plus_deconv(cfg, is_train, **kwargs):
     return PoseShuffleNetV2PlusDeconvHip(cfg, **kwargs)
 
 
-class PoseMobileNetV3PixelShuffleHip(PoseNetHip):
+class PoseMobileNetV3PixelShuffleHip(_Trainable, PoseNetHip):
     """pose_mobilenetv3_small_pixel_shuffle (deep_hrnet/lib/models/pose_mobilenetv3_small_pixel_shuffle.py:23-52:
     torchvision's MobileNetV3-small ``features`` -- hard-swish, 3x3 / 5x5 depthwise convs, squeeze-excitation with
-    biases, BatchNorm eps 1e-3 --, the pixel-shuffle (DUC) decoder, ``final_layer``) inference through the same C ABI;
+    biases, BatchNorm eps 1e-3 --, the pixel-shuffle (DUC) decoder, ``final_layer``) through the same C ABI;
     ``state_dict`` in the reference module's key format (``backbone.0.*``).  MODEL_SIZE 'large' is refused (the
-    reference cannot run it either).  Storage modes "f32" and "f16x2"."""
+    reference cannot run it either).  Storage modes "f32" and "f16x2".  ``trainable`` (what
+    ``MODELS[NAME](cfg, is_train=True)`` sets): the model also has the training surface of ``PoseShuffleNetV2Hip`` --
+    ``init_weights``, ``train()``, ``parameters()``, ``trainer()`` (a train.MobileNetV3Trainer, fp32 whatever the
+    storage mode of the inference program)."""
 
     NAME = "pose_mobilenetv3_small_pixel_shuffle"
     DTYPES = ("f32", "f16x2")
+    TRAINS = True                # a net of this class can be built trainable
+    TRAINER = "MobileNetV3Trainer"
 
-    def __init__(self, cfg, dtype="f32"):
+    def __init__(self, cfg, dtype="f32", trainable=False):
         if dtype not in self.DTYPES:
             raise NotImplementedError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
         super().__init__(cfg, dtype)
@@ -854,6 +859,7 @@ class PoseMobileNetV3PixelShuffleHip(PoseNetHip):
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
         self.spec = self._spec_of(self.extra, self.num_joints, self.target_type)   # NotImplementedError for 'large' ...
+        self.trainable = bool(trainable) and self.TRAINS
 
     @staticmethod
     def _spec_of(extra, num_joints, target_type):
@@ -867,7 +873,69 @@ class PoseMobileNetV3PixelShuffleHip(PoseNetHip):
                                            architecture=sp["architecture"], final_kernel=sp["final_kernel"])
 
     def init_weights(self, pretrained=""):
-        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+        """What the reference's constructor leaves behind (the pose modules have no ``init_weights`` of their own).  The
+        backbone is torchvision's ``MobileNetV3.__init__``: every Conv2d -- depthwise and squeeze-excitation included --
+        ``kaiming_normal_(mode="fan_out")`` = N(0, 2 / (shape[0] k k)), conv biases 0, BatchNorm 1 / 0.  Decoder / deconv
+        head / ``final_layer`` keep torch's nn.Conv2d / ConvTranspose2d / BatchNorm2d defaults, as in
+        ``PoseShuffleNetV2Hip.init_weights``.  The reference hands any truthy ``PRETRAINED`` to torchvision, which
+        downloads ImageNet weights (backbones/mobilenetv3.py:5-10; the recipe's value is the string "yes please"); this
+        code never reaches for the network: a ``pretrained`` that names a file on disk is read as torchvision's own
+        checkpoint -- a bare state_dict or one under "state_dict", ``module.`` stripped, ``features.N.`` ->
+        ``backbone.0.N.``, ``classifier.*`` ignored, non-strict by name and size --, any other truthy value keeps the
+        constructor initialisation and logs one warning.  Draws come from torch's global generator."""
+        import logging
+        import math
+        import os
+        if not self.trainable:
+            raise NotImplementedError("%s: built with is_train=False (inference only); load a state_dict" % self.NAME)
+        shapes = self.param_shapes()
+        sd = {}
+        for k, shape in shapes.items():
+            backbone = k.startswith("backbone.")
+            bn = (k.rsplit(".", 1)[0] + ".running_mean") in shapes
+            if k.endswith("num_batches_tracked"):
+                sd[k] = torch.zeros((), dtype=torch.int64)
+            elif k.endswith("running_var"):
+                sd[k] = torch.ones(shape)
+            elif k.endswith("running_mean"):
+                sd[k] = torch.zeros(shape)
+            elif bn:
+                sd[k] = torch.ones(shape) if k.endswith(".weight") else torch.zeros(shape)
+            elif backbone and len(shape) == 4:
+                sd[k] = torch.randn(shape) * math.sqrt(2.0 / (shape[0] * shape[2] * shape[3]))
+            elif backbone:
+                sd[k] = torch.zeros(shape)                    # the squeeze-excitation's conv biases
+            else:                                             # nn.Conv2d / nn.ConvTranspose2d defaults, weight before bias
+                w = shapes[k.rsplit(".", 1)[0] + ".weight"]
+                bound = 1.0 / math.sqrt(w[1] * w[2] * w[3])   # (ConvTranspose2d: torch takes fan_in from dim 1 there too)
+                sd[k] = (torch.rand(shape) * 2 - 1) * bound
+        if pretrained and isinstance(pretrained, str) and os.path.isfile(pretrained):
+            ckpt = torch.load(pretrained, map_location="cpu", weights_only=True)
+            if isinstance(ckpt, dict) and isinstance(ckpt.get("state_dict"), dict):
+                ckpt = ckpt["state_dict"]
+            for name, v in ckpt.items():
+                name = name[7:] if name.startswith("module.") else name
+                if not name.startswith("features."):
+                    continue                                  # classifier.* and anything else that is not the backbone
+                name = "backbone.0." + name[len("features."):]
+                if name in sd and tuple(v.shape) == tuple(sd[name].shape):
+                    sd[name] = v                              # non-strict: a missing or differently sized tensor keeps its init
+        elif pretrained:
+            logging.getLogger(__name__).warning(
+                "%s: MODEL.PRETRAINED=%r is not a file; the reference would download torchvision's ImageNet weights here -- "
+                "keeping the constructor initialisation", self.NAME, pretrained)
+        return self._set_weights(sd)
+
+    def trainer(self):
+        if not self.trainable:
+            raise NotImplementedError("%s: built with is_train=False (inference only); MODELS[%r](cfg, is_train=True) "
+                                      "returns the trainable model" % (self.NAME, self.NAME))
+        return super().trainer()
+
+    def _make_trainer(self):
+        from . import train
+        return getattr(train, self.TRAINER)(self.spec, self.num_joints, self.target_type, self._sd, device=self.device,
+                                            dtype="f32")
 
     def _make_program(self, h, w):
         from .mobilenetv3_plan import MobileNetV3Program
@@ -875,9 +943,10 @@ class PoseMobileNetV3PixelShuffleHip(PoseNetHip):
 
 
 def get_pose_net_mobilenetv3_pixel_shuffle(cfg, is_train, **kwargs):
-    """pose_mobilenetv3_small_pixel_shuffle.py:55-64 (``get_pose_net``); inference only -- the weights come from
-    ``load_state_dict`` (the reference downloads ImageNet weights under is_train; training is out of scope)."""
-    return PoseMobileNetV3PixelShuffleHip(cfg, **kwargs)
+    """pose_mobilenetv3_small_pixel_shuffle.py:55-64 (``get_pose_net``): trainable under ``is_train``
+    (``init_weights(cfg.MODEL.PRETRAINED)`` when cfg.MODEL.INIT_WEIGHTS says so -- without the reference's download);
+    otherwise the weights come from ``load_state_dict``."""
+    return _init_under_is_train(PoseMobileNetV3PixelShuffleHip(cfg, trainable=bool(is_train), **kwargs), cfg, is_train)
 
 
 class PoseMobileNetV3Hip(PoseMobileNetV3PixelShuffleHip):
@@ -885,6 +954,7 @@ class PoseMobileNetV3Hip(PoseMobileNetV3PixelShuffleHip):
     of pose_resnet -- three ConvTranspose2d(4, 2, 1) + BN + ReLU, ``final_layer``."""
 
     NAME = "pose_mobilenetv3_small"
+    TRAINER = "MobileNetV3DeconvTrainer"
 
     @staticmethod
     def _spec_of(extra, num_joints, target_type):
@@ -899,8 +969,8 @@ class PoseMobileNetV3Hip(PoseMobileNetV3PixelShuffleHip):
 
 
 def get_pose_net_mobilenetv3(cfg, is_train, **kwargs):
-    """pose_mobilenetv3_small.py (``get_pose_net``); inference only -- the weights come from ``load_state_dict``."""
-    return PoseMobileNetV3Hip(cfg, **kwargs)
+    """pose_mobilenetv3_small.py (``get_pose_net``): trainable under ``is_train``, like the pixel-shuffle net."""
+    return _init_under_is_train(PoseMobileNetV3Hip(cfg, trainable=bool(is_train), **kwargs), cfg, is_train)
 
 
 MODELS = {"pose_hrnet": get_pose_net, "pose_hrnet_psa": get_pose_net_psa, "pose_resnet": get_pose_net_resnet,

@@ -5,7 +5,8 @@ the gradient of the whole model is ONE contiguous bucket for the RCCL all-reduce
 of the train-mode forward its subclass runs op by op through the C ABI, walks it backwards
 (``loss.backward()``), then ``udp_adam_step`` (``optimizer.step()``).  ``HRNetTrainer`` is the graph of
 lib/models/pose_hrnet.py:436-471 (and pose_hrnet_psa), ``PoseResNetTrainer`` that of lib/models/pose_resnet.py:195-209,
-``ShuffleNetV2Trainer`` / ``ShuffleNetV2DeconvTrainer`` those of the two ShuffleNetV2 pose nets.
+``ShuffleNetV2Trainer`` / ``ShuffleNetV2DeconvTrainer`` those of the two ShuffleNetV2 pose nets, ``MobileNetV3Trainer`` /
+``MobileNetV3DeconvTrainer`` those of the two MobileNetV3-small pose nets.
 torch is used for device memory only; every arithmetic step is a kernel of libudp_pose_hip.so.
 
 Reference contract mirrored: ``JointsMSELoss`` / ``JointsMSELoss_offset`` (lib/core/loss.py),
@@ -325,14 +326,14 @@ class Trainer:
         self._tape.append((y, backward, y_keep, [name + ".weight"] + ([bias_key] if bias_key else [])))
         return y
 
-    def _bn(self, x, name, relu=True, res=None):
+    def _bn(self, x, name, relu=True, res=None, eps=BN_EPS, momentum=BN_MOMENTUM):
         L = _lib.lib()
         m, c = x.n * x.h * x.w, x.ck
         if x.c != x.ck and not self.bn_over_stored:
             raise ValueError("%s: BatchNorm over %d channels (not a multiple of 16)" % (name, x.c))
         y = self._new(x.n, x.h, x.w, x.c)
         save = torch.empty(2 * c, dtype=torch.float32, device=self.device)
-        args = (x.buf.data_ptr(), m, c, self._p(name + ".weight"), self._p(name + ".bias"), BN_EPS, BN_MOMENTUM,
+        args = (x.buf.data_ptr(), m, c, self._p(name + ".weight"), self._p(name + ".bias"), eps, momentum,
                 self._p(name + ".running_mean"), self._p(name + ".running_var"), save.data_ptr(), save.data_ptr() + 4 * c,
                 None if res is None else res.buf.data_ptr(), int(relu), y.buf.data_ptr(), self._dt,
                 (x.bn_ws if x.bn_rows else self._bn_ws).data_ptr())
@@ -1326,3 +1327,190 @@ class ShuffleNetV2DeconvTrainer(ShuffleNetV2Trainer):
             a = self._bn(self._deconv(a, q, q + ".bias" if self.spec["deconv_with_bias"] else None),
                          "deconv_layers.%d" % (3 * d + 1))
         return a
+
+
+class MobileNetV3Trainer(ShuffleNetV2Trainer):
+    """pose_mobilenetv3_small_pixel_shuffle (deep_hrnet/lib/models/pose_mobilenetv3_small_pixel_shuffle.py:23-52; recipe
+    experiments/coco/mobilenetv3/small_256x192_adam_lr1e-3_pixel_shuffle.yaml) on the base step.  ``spec``: the dict of
+    ``mobilenetv3_plan.mobilenetv3_ps_spec``.  The backbone is torchvision's ``mobilenet_v3_small().features``
+    (backbones/mobilenetv3.py:5-16), i.e. the block table ``synth_mobilenetv3.BLOCKS``; its BatchNorms run with
+    eps 1e-3 / momentum 0.01 (torchvision's ``partial(nn.BatchNorm2d, eps=0.001, momentum=0.01)``), the heads keep
+    1e-5 / 0.1.  fp32 only: the reference's precision, and the depthwise / squeeze-excitation kernels have no bf16 form.
+
+    What it takes from ``ShuffleNetV2Trainer``: the padded layout (``_key_stride``, ``bn_over_stored`` -- 72, 88, 120, 24
+    and 40 channels are stored as 80, 96, 128, 32 and 48), ``_pixshuf`` and the head.  The depthwise weights and the
+    squeeze-excitation's ``fc1`` / ``fc2`` are read by their kernels as they are (no pack step); their gradients land in
+    ``grad`` under their own keys."""
+
+    NAME = "pose_mobilenetv3_small_pixel_shuffle"
+    BACKBONE_BN = dict(eps=1e-3, momentum=0.01)
+
+    def __init__(self, spec, num_joints, target_type, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-8, bucket_elems=6 * 1024 * 1024):
+        from .synth_mobilenetv3 import BLOCKS
+        if dtype != "f32":
+            raise ValueError("%s trains in fp32 only (dtype %r): the depthwise and squeeze-excitation kernels have no bf16 "
+                             "form" % (self.NAME, dtype))
+        self.spec = dict(spec)
+        self._blocks = BLOCKS
+        shapes = self._head_shapes(num_joints, target_type)
+        Trainer.__init__(self, shapes, state_dict, num_joints, target_type, device=device, dtype=dtype, lr=lr, betas=betas,
+                         eps=eps, bucket_elems=bucket_elems)
+        # one workspace for every depthwise weight gradient (they run in order on the side stream): the widest split
+        L = _lib.lib()
+        self._dw_ws = torch.empty(max(int(L.udp_dwconvk_wgrad_workspace_bytes(256, 1, 1, _rup(s[0], 16), s[2]))
+                                      for k, s in shapes.items() if self._is_dw(k, s)), dtype=torch.uint8, device=self.device)
+
+    def _head_shapes(self, num_joints, target_type):
+        from .synth_mobilenetv3 import mobilenetv3_ps_param_shapes
+        sp = self.spec
+        if any(a % 64 for a in sp["architecture"]):
+            raise ValueError("%s trainer: ARCHITECTURE=%s -- the pixel shuffle moves 16 input channels per thread, every entry "
+                             "must be a multiple of 64" % (self.NAME, tuple(sp["architecture"])))
+        return mobilenetv3_ps_param_shapes(num_joints=int(num_joints), target_type=target_type,
+                                           start_channels=sp["start_channels"], architecture=tuple(sp["architecture"]),
+                                           final_kernel=sp["final_kernel"])
+
+    @staticmethod
+    def _is_dw(key, shape):
+        return len(shape) == 4 and shape[1] == 1 and shape[2] > 1 and key.startswith("backbone.0.")
+
+    def _conv_entry(self, key, shape):
+        if self._is_dw(key, shape) or ".fc1." in key or ".fc2." in key:
+            return None                     # the depthwise and squeeze-excitation kernels read the parameters as they are
+        if key.startswith("deconv_layers."):
+            return shape[1], shape[0], shape[2], True, True       # ConvTranspose2d.weight is [cin][cout][k][k]
+        return shape[0], shape[1], shape[2], False, key != "backbone.0.0.0.weight"
+
+    # ------------------------------------------------------------------ the ops the other nets do not have
+    def _dwk(self, x, name, ks, stride):
+        """Depthwise ks x ks (the depthwise member of an InvertedResidual) straight from the parameter."""
+        L = _lib.lib()
+        key = name + ".weight"
+        c_real = self._shapes[key][0]
+        if x.c != c_real or self._shapes[key][2] != ks:
+            raise ValueError("%s: expects %d channels and a %dx%d kernel, got %d and %s" % (name, c_real, ks, ks, x.c, self._shapes[key]))
+        y = self._new(x.n, (x.h - 1) // stride + 1, (x.w - 1) // stride + 1, x.c)
+        _lib.check(L.udp_dwconvk_train_fwd(x.buf.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, ks, stride, self._dt,
+                                           y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            dy = y.grad
+            wgrad = lambda: _lib.check(L.udp_dwconvk_wgrad(
+                x.buf.data_ptr(), dy.data_ptr(), x.n, x.h, x.w, x.ck, c_real, ks, stride, self._dt, self._g(key),
+                self._dw_ws.data_ptr(), self._dw_ws.numel(), self._stream()))
+            self._on_side(wgrad, dy, x.buf)
+            if not x.needs_grad:
+                return
+            have = x.grad is not None
+            if not have:
+                x.grad = self._like(x)
+            _lib.check(L.udp_dwconvk_dgrad(dy.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, ks, stride, int(have),
+                                           self._dt, x.grad.data_ptr(), self._stream()))
+        self._tape.append((y, backward, None, [key]))
+        return y
+
+    def _hswish(self, x):
+        """nn.Hardswish behind a BatchNorm that ran with relu=False; ``x`` stays on the tape for the derivative."""
+        L = _lib.lib()
+        y = self._new(x.n, x.h, x.w, x.c)
+        _lib.check(L.udp_hswish_fwd(x.buf.data_ptr(), y.buf.data_ptr(), x.buf.numel(), self._stream()))
+
+        def backward():
+            self._one_consumer("hard-swish", x)
+            x.grad = self._like(x)
+            _lib.check(L.udp_hswish_bwd(y.grad.data_ptr(), x.buf.data_ptr(), x.grad.data_ptr(), x.buf.numel(), self._stream()))
+        self._tape.append((y, backward, None, []))
+        return y
+
+    def _bn_act(self, x, name, hs):
+        """A backbone BatchNorm + its activation: ReLU inside the BatchNorm kernels, hard-swish as one more launch."""
+        if not hs:
+            return self._bn(x, name, **self.BACKBONE_BN)
+        return self._hswish(self._bn(x, name, relu=False, **self.BACKBONE_BN))
+
+    def _se(self, x, name):
+        """torchvision.ops.SqueezeExcitation ``name`` (fc1 / fc2 with biases) in train mode."""
+        L = _lib.lib()
+        keys = [name + k for k in (".fc1.weight", ".fc1.bias", ".fc2.weight", ".fc2.bias")]
+        sq = self._shapes[keys[0]][0]
+        if tuple(self._shapes[keys[0]]) != (sq, x.c, 1, 1) or tuple(self._shapes[keys[2]]) != (x.c, sq, 1, 1):
+            raise ValueError("%s: squeeze-excitation over %d channels, weights %s / %s" % (name, x.c, self._shapes[keys[0]], self._shapes[keys[2]]))
+        pool = torch.empty(x.n * x.ck, dtype=torch.float32, device=self.device)
+        hid = torch.empty(x.n * sq, dtype=torch.float32, device=self.device)
+        s = torch.empty(x.n * x.ck, dtype=torch.float32, device=self.device)
+        y = self._new(x.n, x.h, x.w, x.c)
+        _lib.check(L.udp_se_train_fwd(x.buf.data_ptr(), *[self._p(k) for k in keys], x.n, x.h, x.w, x.ck, x.c, sq, self._dt,
+                                      pool.data_ptr(), hid.data_ptr(), s.data_ptr(), y.buf.data_ptr(), self._stream()))
+
+        def backward():
+            have = x.grad is not None
+            if not have:
+                x.grad = self._like(x)
+            ws = torch.empty(int(L.udp_se_train_workspace_bytes(x.n, x.ck, sq)), dtype=torch.uint8, device=self.device)
+            _lib.check(L.udp_se_train_bwd(y.grad.data_ptr(), x.buf.data_ptr(), self._p(keys[0]), self._p(keys[2]), pool.data_ptr(),
+                                          hid.data_ptr(), s.data_ptr(), x.n, x.h, x.w, x.ck, x.c, sq, int(have), self._dt,
+                                          x.grad.data_ptr(), self._g(keys[0]), self._g(keys[1]), self._g(keys[2]), self._g(keys[3]),
+                                          ws.data_ptr(), ws.numel(), self._stream()))
+        self._tape.append((y, backward, (pool, hid, s), keys))
+        return y
+
+    # ------------------------------------------------------------------ the graph (synth_mobilenetv3.BLOCKS)
+    def _block(self, x, i, cin, ks, exp, cout, se, act, stride):
+        """InvertedResidual ``backbone.0.<i>``: expand 1x1 (when exp != in), depthwise ks x ks with the stride, the
+        squeeze-excitation behind the activation, project 1x1 whose BatchNorm has no activation; ``x + block(x)`` when
+        the stride is 1 and in == out (the shortcut is the ``res`` of the project BatchNorm)."""
+        p, m, hs = "backbone.0.%d.block" % i, 0, act == "HS"
+        y = x
+        if exp != cin:
+            y = self._bn_act(self._conv(y, "%s.%d.0" % (p, m), bn_stats=True), "%s.%d.1" % (p, m), hs)
+            m += 1
+        # 3x3 stays on ShuffleNetV2Trainer._dw (udp_dwconv3_*): the K = 3 arm of udp_dwconvk_* has no measurement on this
+        # code that shows it is not slower
+        dw = self._dw(y, "%s.%d.0" % (p, m), stride) if ks == 3 else self._dwk(y, "%s.%d.0" % (p, m), ks, stride)
+        y = self._bn_act(dw, "%s.%d.1" % (p, m), hs)
+        m += 1
+        if se:
+            y = self._se(y, "%s.%d" % (p, m))
+            m += 1
+        res = x if stride == 1 and cin == cout else None
+        return self._bn(self._conv(y, "%s.%d.0" % (p, m), bn_stats=True), "%s.%d.1" % (p, m), relu=False, res=res,
+                        **self.BACKBONE_BN)
+
+    def forward(self, x):
+        """Train-mode forward.  x: fp32 [N,3,H,W] on the device.  Returns fp32 [N,C,H/4,W/4]."""
+        L = _lib.lib()
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+            raise ValueError("expected contiguous fp32 [N,3,H,W]")
+        n, _, h, w = x.shape
+        if h % 32 or w % 32:
+            raise ValueError("input %dx%d must be a multiple of 32" % (h, w))
+        self._tape = []
+        _lib.check(L.udp_pack_conv_weights_batch(self._pack_table.data_ptr(), len(self._convs), self._dt, self._stream()))
+        a = self._new(n, h, w, 3, needs_grad=False)
+        _lib.check(L.udp_nchw_to_nhwc(x.data_ptr(), n, 3, h, w, a.ck, a.buf.data_ptr(), self._dt, self._stream()))
+        a = self._bn_act(self._conv(a, "backbone.0.0.0", stride=2, bn_stats=True), "backbone.0.0.1", True)
+        for i, blk in enumerate(self._blocks, start=1):
+            a = self._block(a, i, *blk)
+        a = self._bn_act(self._conv(a, "backbone.0.12.0", bn_stats=True), "backbone.0.12.1", True)
+        a = self._head(a)
+        self._out = self._conv(a, "final_layer", bias_key="final_layer.bias", nchw_out=True)
+        return self._out.buf
+
+
+class MobileNetV3DeconvTrainer(MobileNetV3Trainer):
+    """pose_mobilenetv3_small (pose_mobilenetv3_small.py; recipe experiments/coco/mobilenetv3/small_256x192_adam_lr1e-3.yaml):
+    the same backbone, the deconv head of pose_resnet behind ``backbone.0.12``.  ``spec``: ``mobilenetv3_plan.mobilenetv3_deconv_spec``."""
+
+    NAME = "pose_mobilenetv3_small"
+
+    def _head_shapes(self, num_joints, target_type):
+        from .synth_mobilenetv3 import mobilenetv3_deconv_param_shapes
+        sp = self.spec
+        if any(f % 16 for f in sp["deconv_filters"]):
+            raise ValueError("%s trainer: deconv filters in multiples of 16 (got %s)" % (self.NAME, tuple(sp["deconv_filters"])))
+        return mobilenetv3_deconv_param_shapes(num_joints=int(num_joints), target_type=target_type,
+                                               deconv_filters=tuple(sp["deconv_filters"]), final_kernel=sp["final_kernel"],
+                                               deconv_with_bias=sp["deconv_with_bias"])
+
+    _head = ShuffleNetV2DeconvTrainer._head
