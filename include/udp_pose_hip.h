@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define UDP_POSE_ABI_VERSION 19
+#define UDP_POSE_ABI_VERSION 20
 
 enum udp_status {
   UDP_OK = 0,
@@ -804,47 +804,50 @@ int udp_stem7_train_fwd(const void* x, const void* w_fwd, int n, int h, int w, i
 /* ------------------------------------------------------------------------- *
  * Training of the ShuffleNetV2 pose nets (pose_shufflenetv2_10x_pixel_shuffle,
  * pose_shufflenetv2_10x; recipes experiments/coco/shufflenetv2/): the ops their
- * graph has beyond the two steps above (csrc/shufflenet_train.hip).  fp32 only
- * (UDP_F32; anything else is UDP_ERR_UNSUPPORTED).  Symbols only:
- * UDP_POSE_ABI_VERSION stays as it is.
+ * graph has beyond the two steps above (csrc/dw_train.hip, csrc/shufflenet_train.hip).
+ * fp32 only (UDP_F32; anything else is UDP_ERR_UNSUPPORTED).
  *
  * All tensors are NHWC with a stored channel count that is a multiple of 4 (a thread owns 4 consecutive channels and
  * moves 16 bytes).  Every entry point writes EVERY stored channel of its outputs -- padded channels come out as zeros
  * computed from zeros --, uses no atomics, and sums in one order that depends on the shape alone: eager and captured
  * steps are bit-equal, and so are two runs.
  * ------------------------------------------------------------------------- */
-/* Depthwise 3x3 conv, stride 1 | 2, padding 1, no bias, no activation (shufflenetv2.py:54 branch_main.3, :66
- * branch_proj.0 under model.train(); the BatchNorm that follows stays unfolded):
- *   y[n,oy,ox,ch] = sum_{ky,kx} x[n, oy*s+ky-1, ox*s+kx-1, ch] * w[ch][0][ky][kx]
- * as nine fmaf in (ky, kx) order with the taps outside the image skipped -- the contract of the inference kernel
- * (UDP_OP_DWCONV).  x: [n,hin,win,c]; w: the parameter itself, [c_real][1][3][3] fp32, read in place (no pack step),
+/* Depthwise ks x ks conv (ks = 3 | 5), stride 1 | 2, padding ks/2, no bias, no activation (csrc/dw_train.hip;
+ * shufflenetv2.py:54 branch_main.3, :66 branch_proj.0 and the depthwise member of a MobileNetV3 InvertedResidual, BLOCKS
+ * columns `kernel`, `stride`, under model.train(); the BatchNorm that follows stays unfolded):
+ *   y[n,oy,ox,ch] = sum_{ky,kx} x[n, oy*s+ky-ks/2, ox*s+kx-ks/2, ch] * w[ch][0][ky][kx]
+ * as fmaf in (ky, kx) order with the taps outside the image skipped -- the contract of the inference kernel
+ * (UDP_OP_DWCONV).  x: [n,hin,win,c]; w: the parameter itself, [c_real][1][ks][ks] fp32, read in place (no pack step),
  * 16-byte aligned; c_real <= c, channels c_real..c of y are written as zero.  y: [n,hout,wout,c] with
- * hout = (hin-1)/s + 1 (odd sizes allowed).  Stride other than 1 | 2: UDP_ERR_UNSUPPORTED. */
-int udp_dwconv3_train_fwd(const void* x, const void* w, int n, int hin, int win, int c, int c_real, int stride, int dtype,
-                          void* y, void* stream);
-/* Its input gradient (autograd's backward of :54 / :66 w.r.t. the input):
- *   dx[n,iy,ix,ch] (+)= sum_{ky,kx} dy[n, (iy+1-ky)/s, (ix+1-kx)/s, ch] * w[ch][ky][kx]
- * over the taps where the division is exact and the index lies inside dy [n,hout,wout,c].  A gather: one thread owns an
- * input pixel x 4 channels.  `accumulate` != 0 adds the sum to dx (the input of a stride-2 unit feeds both branches,
- * :81-84); otherwise every element of dx [n,hin,win,c] is overwritten. */
-int udp_dwconv3_dgrad(const void* dy, const void* w, int n, int hin, int win, int c, int c_real, int stride, int accumulate,
-                      int dtype, void* dx, void* stream);
-/* Its weight gradient, written in the parameter layout [c_real][1][3][3] (nothing is accumulated):
- *   dw[ch][ky][kx] = sum_{n,y,x} dy[n,y,x,ch] * x[n, y*s+ky-1, x*s+kx-1, ch]
+ * hout = (hin-1)/s + 1 (odd sizes allowed).  A thread owns a strip of consecutive output pixels of one row (2 for 3x3, 4
+ * for 5x5) x 4 channels and loads each input column of a kernel row once for the whole strip.  ks other than 3 | 5,
+ * stride other than 1 | 2: UDP_ERR_UNSUPPORTED. */
+int udp_dwconvk_train_fwd(const void* x, const void* w, int n, int hin, int win, int c, int c_real, int ks, int stride,
+                          int dtype, void* y, void* stream);
+/* Its input gradient (autograd's backward w.r.t. the input), a gather over a strip of input pixels:
+ *   dx[n,iy,ix,ch] (+)= sum_{ky,kx} dy[n, (iy+ks/2-ky)/s, (ix+ks/2-kx)/s, ch] * w[ch][ky][kx]
+ * over the taps where both divisions are exact and the index lies inside dy [n,hout,wout,c]; (ky, kx) order from 0.
+ * `accumulate` != 0 adds the sum to dx last (the input of a stride-2 ShuffleNetV2 unit feeds both branches, :81-84);
+ * otherwise every element of dx [n,hin,win,c] is overwritten. */
+int udp_dwconvk_dgrad(const void* dy, const void* w, int n, int hin, int win, int c, int c_real, int ks, int stride,
+                      int accumulate, int dtype, void* dx, void* stream);
+/* Its weight gradient, written in the parameter layout [c_real][1][ks][ks] (nothing is accumulated):
+ *   dw[ch][ky][kx] = sum_{n,y,x} dy[n,y,x,ch] * x[n, y*s+ky-ks/2, x*s+kx-ks/2, ch]
  * Two launches.  The n*hout output rows are cut into `partials` runs of `rows` consecutive rows; a workgroup takes one
- * run and up to 64 channel groups (lanes along channels, 9 taps x 4 channels of fp32 accumulators per thread, its pixel
- * lanes combined through LDS in lane order) and leaves a [9][c] partial in the workspace; the second launch adds the
- * partials in index order.  partials = min(n*hout, 256, workspace_bytes / (36 c)), rows = ceil(n*hout / partials),
- * partials = ceil(n*hout / rows): a pure function of the shape and the workspace size.  A workspace that holds no
- * partial: UDP_ERR_WORKSPACE.  udp_dwconv3_wgrad_workspace_bytes: what the unconstrained split needs (0: bad shape);
- * never more than 256 * 36 * c bytes, which (n = 256, hout = 1) returns. */
-size_t udp_dwconv3_wgrad_workspace_bytes(int n, int hout, int wout, int c);
-int udp_dwconv3_wgrad(const void* x, const void* dy, int n, int hin, int win, int c, int c_real, int stride, int dtype,
+ * run and up to 64 channel groups (lanes along channels, ks^2 taps x 4 channels of fp32 accumulators per thread, its
+ * pixel lanes combined through LDS in lane order, one kernel row at a time) and leaves a [ks^2][c] partial in the
+ * workspace; the second launch adds the partials in index order.  partials = min(n*hout, 256, workspace_bytes /
+ * (4 ks^2 c)), rows = ceil(n*hout / partials), partials = ceil(n*hout / rows): a pure function of the shape and the
+ * workspace size.  A workspace that holds no partial: UDP_ERR_WORKSPACE.  udp_dwconvk_wgrad_workspace_bytes: what the
+ * unconstrained split needs (0: bad shape or ks; udp_last_error() is left as it was), never more than 256 * 4 ks^2 c
+ * bytes, which (n = 256, hout = 1) returns. */
+size_t udp_dwconvk_wgrad_workspace_bytes(int n, int hout, int wout, int c, int ks);
+int udp_dwconvk_wgrad(const void* x, const void* dy, int n, int hin, int win, int c, int c_real, int ks, int stride, int dtype,
                       void* dw, void* workspace, size_t workspace_bytes, void* stream);
-/* Host only: the split udp_dwconv3_wgrad would use (it calls the same function).  out[0] = output rows per workgroup,
+/* Host only: the split udp_dwconvk_wgrad would use (it calls the same function).  out[0] = output rows per workgroup,
  * out[1] = workgroups of the first launch (partials x channel blocks), out[2] = partials, out[3] = LDS bytes of a
- * workgroup.  Returns what the launch would return for this shape and workspace. */
-int udp_debug_dw_wgrad_plan(int n, int hout, int wout, int c, size_t workspace_bytes, int* out);
+ * workgroup (256 * ks * 16).  Returns what the launch would return for this shape, ks and workspace. */
+int udp_debug_dw_wgrad_plan(int n, int hout, int wout, int c, int ks, size_t workspace_bytes, int* out);
 /* nn.PixelShuffle(2) in torch's own channel order (decoders/DUC.py:27 under model.train()) and its backward:
  *   y[n, 2h+i, 2w+j, ch] = x[n, h, w, 4ch + 2i + j]          x: [n,h,w,cin], y: [n,2h,2w,cin/4]
  * _bwd is the inverse: dy [n,2h,2w,cin/4] -> dx [n,h,w,cin]; h, w, cin describe the LOW-resolution tensor in both.
@@ -876,37 +879,14 @@ int udp_chan_uncat2(const void* y, int c, int64_t m, int dtype, void* a, int pa,
  * deep_hrnet/lib/models/backbones/mobilenetv3.py:5-16; the block table is
  * udp_pose_amd/synth_mobilenetv3.py BLOCKS -- adds to a ShuffleNetV2 step
  * (csrc/mobilenetv3_train.hip).  fp32 only (UDP_F32; anything else is
- * UDP_ERR_UNSUPPORTED).  Symbols only: UDP_POSE_ABI_VERSION stays as it is.
+ * UDP_ERR_UNSUPPORTED).
  *
  * The conventions of the section above hold: NHWC tensors with a stored channel count c % 4 == 0, c_real <= c real
  * channels first; every stored channel of every output is written and the padded ones are exact zeros; no atomics, one
  * summation order per shape (two runs, and eager and captured steps, are bit-equal); no host synchronisation and no
  * allocation (capturable in a hipGraph); every argument check comes before anything touches the device.
  * ------------------------------------------------------------------------- */
-/* Depthwise ks x ks conv (ks = 3 | 5), stride 1 | 2, padding ks/2, no bias, no activation (the depthwise member of an
- * InvertedResidual under model.train(); BLOCKS columns `kernel`, `stride`): the contract of udp_dwconv3_train_fwd with
- * a kernel size --
- *   y[n,oy,ox,ch] = sum_{ky,kx} x[n, oy*s+ky-ks/2, ox*s+kx-ks/2, ch] * w[ch][0][ky][kx]
- * as fmaf in (ky, kx) order with the taps outside the image skipped.  w: the parameter itself, [c_real][1][ks][ks]
- * fp32, read in place, 16-byte aligned.  A thread owns a strip of consecutive output pixels of one row (2 for 3x3, 4
- * for 5x5) x 4 channels and loads each input column of a kernel row once for the whole strip.  ks other than 3 | 5,
- * stride other than 1 | 2: UDP_ERR_UNSUPPORTED. */
-int udp_dwconvk_train_fwd(const void* x, const void* w, int n, int hin, int win, int c, int c_real, int ks, int stride,
-                          int dtype, void* y, void* stream);
-/* Its input gradient, a gather like udp_dwconv3_dgrad:
- *   dx[n,iy,ix,ch] (+)= sum_{ky,kx} dy[n, (iy+ks/2-ky)/s, (ix+ks/2-kx)/s, ch] * w[ch][ky][kx]
- * over the taps where both divisions are exact and the index lies inside dy [n,hout,wout,c]; (ky, kx) order from 0,
- * `accumulate` != 0 adds the sum to dx last. */
-int udp_dwconvk_dgrad(const void* dy, const void* w, int n, int hin, int win, int c, int c_real, int ks, int stride,
-                      int accumulate, int dtype, void* dx, void* stream);
-/* Its weight gradient in the parameter layout [c_real][1][ks][ks] (overwritten), with the fixed row split of
- * udp_dwconv3_wgrad: partials = min(n*hout, 256, workspace_bytes / (4 ks^2 c)), rows = ceil(n*hout / partials),
- * partials = ceil(n*hout / rows); [ks^2][c] partials in the workspace, added in index order by a second launch.  A
- * workspace that holds no partial: UDP_ERR_WORKSPACE.  udp_dwconvk_wgrad_workspace_bytes: what the unconstrained split
- * needs (0: bad shape or ks), never more than 256 * 4 ks^2 c bytes, which (n = 256, hout = 1) returns. */
-size_t udp_dwconvk_wgrad_workspace_bytes(int n, int hout, int wout, int c, int ks);
-int udp_dwconvk_wgrad(const void* x, const void* dy, int n, int hin, int win, int c, int c_real, int ks, int stride, int dtype,
-                      void* dw, void* workspace, size_t workspace_bytes, void* stream);
+/* The depthwise convs of the InvertedResiduals are the udp_dwconvk_* of the section above. */
 /* nn.Hardswish (BLOCKS column `activation` = "HS", and behind the stem and the last conv) over `count` fp32 values,
  * count a positive multiple of 4:  y = x * clamp(x + 3, 0, 6) / 6;
  *   dx = 0 (x < -3) | dy * (x / 3 + 0.5) (-3 <= x <= 3) | dy (x > 3)      (x: the forward's INPUT).

@@ -1,4 +1,4 @@
-"""The MobileNetV3 training kernels (csrc/mobilenetv3_train.hip), one entry point at a time, against fp64 autograd of
+"""The MobileNetV3 training kernels (csrc/dw_train.hip, csrc/mobilenetv3_train.hip), one entry point at a time, against fp64 autograd of
 the same op on the CPU: depthwise 3x3 / 5x5 forward, input gradient and weight gradient (F.conv2d(groups=C)), hard-swish
 (x * clamp(x + 3, 0, 6) / 6, which is F.hardswish) and the squeeze-and-excitation with biases (the formula of tests/mobilenetv3_ref.py:squeeze_excitation;
 torchvision is not installed, so its own module cannot be the arbiter), at the smallest shapes where each can go wrong.
@@ -8,6 +8,9 @@ back fully written and the guards untouched.  The gate is the rule of tests/test
 not chosen: ours may be at most 4 x as far from fp64 as torch's fp32 CPU run of the same op is, or 1e-4 * max|ref| where
 that is more (fp32 CPU error can be zero on tiny tensors).  Pads of every output are exactly zero, two runs are
 bit-identical."""
+import os
+
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -144,10 +147,50 @@ def test_dw_forward_dgrad_and_wgrad_against_fp64(ks, stride):
                     assert _same_bits(_dw_wgrad(x, dy, cs, ks, stride, ws_bytes), dw), tag
 
 
+def _replay_parent_bits(g):
+    """udp_dwconvk_*(ks=3) on the recorded inputs of tests/golden/dw3_train_parent_bits.npz (tools/gen_golden_dw3_parent.py:
+    int32 bit patterns of NHWC fp32 buffers): {name: int32 array} under the fixture's own output names."""
+    L = _lib.lib()
+
+    def dev(name):
+        return torch.from_numpy(g[name]).cuda().view(torch.float32)
+
+    def bits(arena, what):
+        return arena.get(what).view(torch.int32).numpy().reshape(-1)
+
+    got = {}
+    n, h, w, cs, cr = 3, 7, 9, 32, 24
+    x, prev, wt = dev("a_x"), dev("a_prev"), dev("a_w")
+    for s in (1, 2):
+        ho, wo = _out_hw(h, w, s)
+        dy = dev("a_dy_s%d" % s)
+        y, dx0, dx1, dw = Arena(n * ho * wo * cs), Arena(n * h * w * cs), Arena(n * h * w * cs), Arena(cr * 9)
+        dx1.t.copy_(prev.reshape(-1))
+        ws_bytes = int(L.udp_dwconvk_wgrad_workspace_bytes(n, ho, wo, cs, 3))
+        ws = Arena(ws_bytes // 4)
+        _ok(L.udp_dwconvk_train_fwd(x.data_ptr(), wt.data_ptr(), n, h, w, cs, cr, 3, s, F32, y.ptr(), _s()))
+        _ok(L.udp_dwconvk_dgrad(dy.data_ptr(), wt.data_ptr(), n, h, w, cs, cr, 3, s, 0, F32, dx0.ptr(), _s()))
+        _ok(L.udp_dwconvk_dgrad(dy.data_ptr(), wt.data_ptr(), n, h, w, cs, cr, 3, s, 1, F32, dx1.ptr(), _s()))
+        _ok(L.udp_dwconvk_wgrad(x.data_ptr(), dy.data_ptr(), n, h, w, cs, cr, 3, s, F32, dw.ptr(), ws.ptr(), ws_bytes, _s()))
+        ws.check("dwk wgrad workspace")
+        got.update({"a_y_s%d" % s: bits(y, "fwd"), "a_dx_acc0_s%d" % s: bits(dx0, "dgrad"), "a_dx_acc1_s%d" % s: bits(dx1, "dgrad acc"),
+                    "a_dw_s%d" % s: bits(dw, "wgrad")})
+    cs, cr = 64, 58
+    x, dy, dw, ws_bytes = dev("b_x"), dev("b_dy"), Arena(cr * 9), 5 * 9 * cs * 4           # 21 rows in runs of 5, 5, 5, 5, 1
+    ws = Arena(ws_bytes // 4)
+    _ok(L.udp_dwconvk_wgrad(x.data_ptr(), dy.data_ptr(), n, h, w, cs, cr, 3, 1, F32, dw.ptr(), ws.ptr(), ws_bytes, _s()))
+    ws.check("dwk wgrad workspace")
+    got["b_dw_ws5"] = bits(dw, "wgrad ws5")
+    return got
+
+
 @pytest.mark.parametrize("ks", [3, 5])
-def test_dw_k3_arm_is_the_3x3_kernel_and_many_rows_split(ks):
+def test_dw_k3_arm_is_the_3x3_kernel_and_many_rows_split(ks, golden_dir):
     """More output rows than partials fit (320 rows: the 256 cap -> runs of 2), several blocks of strips; and for K = 3
-    the forward and the input gradient equal udp_dwconv3_* bit for bit (the same fmaf order per element)."""
+    the recorded outputs of the one-pixel-per-thread 3x3 kernels this family replaced (udp_dwconv3_*, recorded from the
+    library that had them), bit for bit: forward, input gradient with and without accumulation and weight gradient at
+    both strides, and the weight gradient under a workspace that limits the split (the same fmaf order per element, the
+    same lane-order and index-order sums)."""
     gen = torch.Generator().manual_seed(7 + ks)
     cs, cr, n, h, w = 48, 40, 40, 8, 10
     x, wt, dy = _rand(gen, n, cr, h, w), _rand(gen, cr, 1, ks, ks), _rand(gen, n, cr, h, w)
@@ -158,12 +201,11 @@ def test_dw_k3_arm_is_the_3x3_kernel_and_many_rows_split(ks):
     _gate("dwk dgrad k%d 40x8x10" % ks, _nchw(dx, n, h, w, cs, cr), dx64, dx32)
     _gate("dwk wgrad k%d 40x8x10" % ks, dw, dw64, dw32)
     if ks == 3:
-        L = _lib.lib()
-        xd, dd, wd = _nhwc(x, cs), _nhwc(dy, cs), wt.float().contiguous().cuda()
-        y3, dx3 = Arena(n * h * w * cs), Arena(n * h * w * cs)
-        _ok(L.udp_dwconv3_train_fwd(xd.data_ptr(), wd.data_ptr(), n, h, w, cs, cr, 1, F32, y3.ptr(), _s()))
-        _ok(L.udp_dwconv3_dgrad(dd.data_ptr(), wd.data_ptr(), n, h, w, cs, cr, 1, 0, F32, dx3.ptr(), _s()))
-        assert _same_bits(y3.get("dw3 fwd"), y) and _same_bits(dx3.get("dw3 dgrad"), dx)
+        g = np.load(os.path.join(golden_dir, "dw3_train_parent_bits.npz"))
+        got = _replay_parent_bits(g)
+        assert len(got) == 9 and all(float(np.abs(g[k].view(np.float32)).max()) > 0 for k in got)       # a record of something
+        differ = [(k, int((got[k] != g[k].reshape(-1)).sum())) for k in got if not np.array_equal(got[k], g[k].reshape(-1))]
+        assert not differ, differ
 
 
 # ------------------------------------------------------------------ hard-swish

@@ -1,6 +1,6 @@
-"""The ShuffleNetV2 training kernels (csrc/shufflenet_train.hip), one entry point at a time, against fp64 torch on the
-CPU: depthwise 3x3 forward / input gradient / weight gradient (F.conv2d(groups=C) + autograd), pixel shuffle
-(F.pixel_shuffle), the channel shuffle on pairs of halves and the concat (indexing).
+"""The ShuffleNetV2 training kernels (csrc/dw_train.hip at ks = 3, csrc/shufflenet_train.hip), one entry point at a time,
+against fp64 torch on the CPU: depthwise 3x3 forward / input gradient / weight gradient (F.conv2d(groups=C) + autograd),
+pixel shuffle (F.pixel_shuffle), the channel shuffle on pairs of halves and the concat (indexing).
 
 Every output lives in an arena of one NaN bit pattern between two guards (tests/test_gpu_train_arms.py): it must come back
 fully written and the guards untouched.  Gates: forward and input gradient 3 x (the error of the fp32 CPU evaluation) +
@@ -57,7 +57,7 @@ def _dw_fwd(x, wt, cs, s):
     ho, wo = _out_hw(h, w, s)
     out = Arena(n * ho * wo * cs)
     xd, wd = _nhwc(x, cs), wt.float().contiguous().cuda()          # (held until the result has been read)
-    _ok(_lib.lib().udp_dwconv3_train_fwd(xd.data_ptr(), wd.data_ptr(), n, h, w, cs, cr, s, F32, out.ptr(), _s()))
+    _ok(_lib.lib().udp_dwconvk_train_fwd(xd.data_ptr(), wd.data_ptr(), n, h, w, cs, cr, 3, s, F32, out.ptr(), _s()))
     return out.get("dw fwd"), (n, ho, wo)
 
 
@@ -67,14 +67,14 @@ def _dw_dgrad(dy, wt, cs, s, h, w, prev=None):
     if prev is not None:
         out.t.copy_(_nhwc(prev, cs).reshape(-1))
     dd, wd = _nhwc(dy, cs), wt.float().contiguous().cuda()
-    _ok(_lib.lib().udp_dwconv3_dgrad(dd.data_ptr(), wd.data_ptr(), n, h, w, cs, cr, s, int(prev is not None), F32,
+    _ok(_lib.lib().udp_dwconvk_dgrad(dd.data_ptr(), wd.data_ptr(), n, h, w, cs, cr, 3, s, int(prev is not None), F32,
                                      out.ptr(), _s()))
     return out.get("dw dgrad")
 
 
 def _plan(n, ho, wo, cs, ws):
     out = (C.c_int * 4)()
-    _ok(_lib.lib().udp_debug_dw_wgrad_plan(n, ho, wo, cs, ws, out))
+    _ok(_lib.lib().udp_debug_dw_wgrad_plan(n, ho, wo, cs, 3, ws, out))
     return list(out)
 
 
@@ -83,11 +83,11 @@ def _dw_wgrad(x, dy, cs, s, ws_bytes=None):
     ho, wo = dy.shape[2:]
     L = _lib.lib()
     if ws_bytes is None:
-        ws_bytes = int(L.udp_dwconv3_wgrad_workspace_bytes(n, ho, wo, cs))
+        ws_bytes = int(L.udp_dwconvk_wgrad_workspace_bytes(n, ho, wo, cs, 3))
     ws = Arena(ws_bytes // 4)
     out = Arena(cr * 9)
     xd, dd = _nhwc(x, cs), _nhwc(dy, cs)
-    _ok(L.udp_dwconv3_wgrad(xd.data_ptr(), dd.data_ptr(), n, h, w, cs, cr, s, F32, out.ptr(), ws.ptr(), ws_bytes, _s()))
+    _ok(L.udp_dwconvk_wgrad(xd.data_ptr(), dd.data_ptr(), n, h, w, cs, cr, 3, s, F32, out.ptr(), ws.ptr(), ws_bytes, _s()))
     ws.check("dw wgrad workspace")
     return out.get("dw wgrad").view(cr, 1, 3, 3), _plan(n, ho, wo, cs, ws_bytes)
 
@@ -279,19 +279,19 @@ def test_refusals_return_their_code_with_a_message():
     buf = torch.zeros(4096, device="cuda")
     p = buf.data_ptr()
     cases = [
-        (L.udp_dwconv3_train_fwd, (p, p, 1, 4, 4, 32, 24, 1, BF16, p, _s()), UNSUP),
-        (L.udp_dwconv3_train_fwd, (p, p, 1, 4, 4, 32, 24, 3, F32, p, _s()), UNSUP),
-        (L.udp_dwconv3_train_fwd, (p, p, 1, 4, 4, 30, 24, 1, F32, p, _s()), ARG),
-        (L.udp_dwconv3_train_fwd, (p, p, 1, 4, 4, 32, 33, 1, F32, p, _s()), ARG),
-        (L.udp_dwconv3_train_fwd, (None, p, 1, 4, 4, 32, 24, 1, F32, p, _s()), ARG),
-        (L.udp_dwconv3_dgrad, (p, p, 1, 4, 4, 32, 24, 1, 0, BF16, p, _s()), UNSUP),
-        (L.udp_dwconv3_dgrad, (p, p, 1, 4, 4, 32, 24, 3, 0, F32, p, _s()), UNSUP),
-        (L.udp_dwconv3_dgrad, (p, p, 1, 4, 4, 34, 24, 1, 0, F32, p, _s()), ARG),
-        (L.udp_dwconv3_dgrad, (p, p, 1, 4, 4, 32, 24, 1, 0, F32, None, _s()), ARG),
-        (L.udp_dwconv3_wgrad, (p, p, 1, 4, 4, 32, 24, 1, BF16, p, p, 4096, _s()), UNSUP),
-        (L.udp_dwconv3_wgrad, (p, p, 1, 4, 4, 32, 24, 3, F32, p, p, 4096, _s()), UNSUP),
-        (L.udp_dwconv3_wgrad, (p, p, 1, 4, 4, 32, 24, 1, F32, p, None, 4096, _s()), ARG),
-        (L.udp_dwconv3_wgrad, (p, p, 1, 4, 4, 32, 24, 1, F32, p, p, 9 * 32 * 4 - 4, _s()), WORKSPACE),
+        (L.udp_dwconvk_train_fwd, (p, p, 1, 4, 4, 32, 24, 3, 1, BF16, p, _s()), UNSUP),
+        (L.udp_dwconvk_train_fwd, (p, p, 1, 4, 4, 32, 24, 3, 3, F32, p, _s()), UNSUP),
+        (L.udp_dwconvk_train_fwd, (p, p, 1, 4, 4, 30, 24, 3, 1, F32, p, _s()), ARG),
+        (L.udp_dwconvk_train_fwd, (p, p, 1, 4, 4, 32, 33, 3, 1, F32, p, _s()), ARG),
+        (L.udp_dwconvk_train_fwd, (None, p, 1, 4, 4, 32, 24, 3, 1, F32, p, _s()), ARG),
+        (L.udp_dwconvk_dgrad, (p, p, 1, 4, 4, 32, 24, 3, 1, 0, BF16, p, _s()), UNSUP),
+        (L.udp_dwconvk_dgrad, (p, p, 1, 4, 4, 32, 24, 3, 3, 0, F32, p, _s()), UNSUP),
+        (L.udp_dwconvk_dgrad, (p, p, 1, 4, 4, 34, 24, 3, 1, 0, F32, p, _s()), ARG),
+        (L.udp_dwconvk_dgrad, (p, p, 1, 4, 4, 32, 24, 3, 1, 0, F32, None, _s()), ARG),
+        (L.udp_dwconvk_wgrad, (p, p, 1, 4, 4, 32, 24, 3, 1, BF16, p, p, 4096, _s()), UNSUP),
+        (L.udp_dwconvk_wgrad, (p, p, 1, 4, 4, 32, 24, 3, 3, F32, p, p, 4096, _s()), UNSUP),
+        (L.udp_dwconvk_wgrad, (p, p, 1, 4, 4, 32, 24, 3, 1, F32, p, None, 4096, _s()), ARG),
+        (L.udp_dwconvk_wgrad, (p, p, 1, 4, 4, 32, 24, 3, 1, F32, p, p, 9 * 32 * 4 - 4, _s()), WORKSPACE),
         (L.udp_pixshuf2_train_fwd, (p, 1, 2, 2, 64, BF16, p, _s()), UNSUP),
         (L.udp_pixshuf2_train_fwd, (p, 1, 2, 2, 32, F32, p, _s()), ARG),
         (L.udp_pixshuf2_train_bwd, (p, 1, 2, 2, 64, F32, None, _s()), ARG),

@@ -72,7 +72,7 @@ def test_kind_23_follows_the_header():
     numbered = {k: int(v) for k, v in re.findall(r"\b(UDP_OP_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
     assert re.search(r"\bUDP_OP_SE_ACT\s*=\s*UDP_OP_PRM_DW9\s*\+\s*1\b", hdr)
     assert numbered["UDP_OP_PRM_DW9"] == max(numbered.values()) == 22 and _lib.UDP_OP_SE_ACT == numbered["UDP_OP_PRM_DW9"] + 1 == 23
-    assert _lib.ABI_VERSION == 19 and "#define UDP_POSE_ABI_VERSION 19" in hdr
+    assert _lib.ABI_VERSION == 20 and "#define UDP_POSE_ABI_VERSION 20" in hdr
 
 
 def test_models_has_all_four_names():

@@ -48,12 +48,12 @@ EXPORTS = ("udp_dwconvk_train_fwd", "udp_dwconvk_dgrad", "udp_dwconvk_wgrad", "u
 
 def test_exports_and_abi_version():
     L = _lib.lib()
-    assert L.udp_abi_version() == 19 and _lib.ABI_VERSION == 19
+    assert L.udp_abi_version() == 20 and _lib.ABI_VERSION == 20
     for name in EXPORTS:
         assert getattr(L, name) is not None and name in _lib.EXPORTS, name
     with open(os.path.join(ROOT, "include", "udp_pose_hip.h")) as f:
         header = f.read()
-    assert all((" %s(" % name) in header for name in EXPORTS) and "#define UDP_POSE_ABI_VERSION 19" in header
+    assert all((" %s(" % name) in header for name in EXPORTS) and "#define UDP_POSE_ABI_VERSION 20" in header
     assert "backbones/mobilenetv3.py:5-16" in header and "synth_mobilenetv3.py" in header
     assert max(v for k, v in vars(_lib).items() if k.startswith("UDP_OP_")) == 23 and len(MODELS) == 12
 

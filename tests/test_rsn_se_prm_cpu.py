@@ -18,7 +18,7 @@ def test_kind_numbers_follow_the_header():
     kinds = {k: int(v) for k, v in re.findall(r"\b(UDP_OP_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
     assert (kinds["UDP_OP_SE_RES"], kinds["UDP_OP_PRM_GATE"], kinds["UDP_OP_PRM_DW9"]) == (SE, GATE, DW9) == (20, 21, 22)
     assert sorted(kinds.values()) == list(range(23)), "the next free kind numbers, no gap"
-    assert _lib.ABI_VERSION == 19 and "#define UDP_POSE_ABI_VERSION 19" in hdr
+    assert _lib.ABI_VERSION == 20 and "#define UDP_POSE_ABI_VERSION 20" in hdr
 
 
 def _op(kind, c=32, h=8, w=6, **fields):

@@ -195,33 +195,33 @@ def test_refusals():
 
 
 # ------------------------------------------------------------------ the library
-EXPORTS = ("udp_dwconv3_train_fwd", "udp_dwconv3_dgrad", "udp_dwconv3_wgrad", "udp_dwconv3_wgrad_workspace_bytes",
+EXPORTS = ("udp_dwconvk_train_fwd", "udp_dwconvk_dgrad", "udp_dwconvk_wgrad", "udp_dwconvk_wgrad_workspace_bytes",
            "udp_debug_dw_wgrad_plan", "udp_pixshuf2_train_fwd", "udp_pixshuf2_train_bwd", "udp_shuffle_pair_fwd",
            "udp_shuffle_pair_bwd", "udp_chan_cat2", "udp_chan_uncat2")
 
 
 def test_exports_and_abi_version():
     L = _lib.lib()
-    assert L.udp_abi_version() == 19
+    assert L.udp_abi_version() == 20
     for name in EXPORTS:
         assert getattr(L, name) is not None, name
     with open(os.path.join(ROOT, "include", "udp_pose_hip.h")) as f:
         header = f.read()
-    assert all((" %s(" % name) in header for name in EXPORTS) and "#define UDP_POSE_ABI_VERSION 19" in header
+    assert all((" %s(" % name) in header for name in EXPORTS) and "#define UDP_POSE_ABI_VERSION 20" in header
 
 
 def _plan(n, hout, wout, c, ws=None):
     L = _lib.lib()
     out = (C.c_int * 4)()
     if ws is None:
-        ws = int(L.udp_dwconv3_wgrad_workspace_bytes(n, hout, wout, c))
-    return L.udp_debug_dw_wgrad_plan(n, hout, wout, c, ws, out), list(out), ws
+        ws = int(L.udp_dwconvk_wgrad_workspace_bytes(n, hout, wout, c, 3))
+    return L.udp_debug_dw_wgrad_plan(n, hout, wout, c, 3, ws, out), list(out), ws
 
 
 def test_dw_wgrad_plan_against_a_hand_computation():
     """partials = min(n*hout, 256, workspace / (36 c)); rows = ceil(n*hout / partials); partials = ceil(n*hout / rows);
     workgroups = partials x ceil(c/4 / channel lanes), channel lanes = the power of two in 8..64 that covers c/4."""
-    lds = 256 * 36 * 4
+    lds = 256 * 3 * 16                                                                    # the lanes' 3 taps of one kernel row x 4 channels
     # the largest case of a 256x192 batch-32 step: 116 (128) channels, 32x24 outputs: 1024 rows -> 256 runs of 4, 32 lanes cover 32 groups
     assert _plan(32, 32, 24, 128) == (0, [4, 256, 256, lds], 256 * 9 * 128 * 4)
     # the smallest maps: 2x2 outputs of 2 images at 464 channels: 4 rows -> 4 runs of 1; 116 groups need two blocks of 64 lanes
@@ -233,8 +233,8 @@ def test_dw_wgrad_plan_against_a_hand_computation():
     assert _plan(3, 7, 9, 96, ws=4 * 9 * 96 * 4)[:2] == (0, [6, 4, 4, lds])               # 4 fit: 6 rows -> 4 runs (6, 6, 6, 3)
     assert _plan(1, 1, 1, 4)[:2] == (0, [1, 1, 1, lds])
     # the bound over all shapes
-    assert int(_lib.lib().udp_dwconv3_wgrad_workspace_bytes(256, 1, 1, 240)) == 256 * 9 * 240 * 4
-    assert int(_lib.lib().udp_dwconv3_wgrad_workspace_bytes(999, 64, 48, 240)) == 256 * 9 * 240 * 4
+    assert int(_lib.lib().udp_dwconvk_wgrad_workspace_bytes(256, 1, 1, 240, 3)) == 256 * 9 * 240 * 4
+    assert int(_lib.lib().udp_dwconvk_wgrad_workspace_bytes(999, 64, 48, 240, 3)) == 256 * 9 * 240 * 4
 
 
 def test_dw_wgrad_plan_refuses_what_the_launch_refuses():
@@ -242,17 +242,17 @@ def test_dw_wgrad_plan_refuses_what_the_launch_refuses():
     assert _plan(3, 7, 9, 96, ws=9 * 96 * 4 - 1)[0] == UDP_ERR_WORKSPACE and "workspace" in L.udp_last_error().decode()
     assert _plan(3, 7, 9, 98, ws=1 << 20)[0] == UDP_ERR_ARG                               # C % 4
     assert _plan(0, 7, 9, 96, ws=1 << 20)[0] == UDP_ERR_ARG
-    assert L.udp_debug_dw_wgrad_plan(3, 7, 9, 96, 1 << 20, None) == UDP_ERR_ARG
-    assert int(L.udp_dwconv3_wgrad_workspace_bytes(3, 7, 9, 98)) == 0
+    assert L.udp_debug_dw_wgrad_plan(3, 7, 9, 96, 3, 1 << 20, None) == UDP_ERR_ARG
+    assert int(L.udp_dwconvk_wgrad_workspace_bytes(3, 7, 9, 98, 3)) == 0
     # the launch itself, on the host: every refusal comes before anything touches the device
     one = C.c_void_p(16)
-    for args, code in (((one, one, 3, 7, 9, 96, 88, 1, _lib.UDP_F32, one, one, 9 * 96 * 4 - 1, None), UDP_ERR_WORKSPACE),
-                       ((one, one, 3, 7, 9, 96, 88, 3, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_UNSUPPORTED),
-                       ((one, one, 3, 7, 9, 96, 88, 1, _lib.UDP_BF16, one, one, 1 << 20, None), UDP_ERR_UNSUPPORTED),
-                       ((one, one, 3, 7, 9, 98, 88, 1, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_ARG),
-                       ((one, one, 3, 7, 9, 96, 97, 1, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_ARG),
-                       ((None, one, 3, 7, 9, 96, 88, 1, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_ARG)):
-        assert L.udp_dwconv3_wgrad(*args) == code and L.udp_last_error(), args
+    for args, code in (((one, one, 3, 7, 9, 96, 88, 3, 1, _lib.UDP_F32, one, one, 9 * 96 * 4 - 1, None), UDP_ERR_WORKSPACE),
+                       ((one, one, 3, 7, 9, 96, 88, 3, 3, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_UNSUPPORTED),
+                       ((one, one, 3, 7, 9, 96, 88, 3, 1, _lib.UDP_BF16, one, one, 1 << 20, None), UDP_ERR_UNSUPPORTED),
+                       ((one, one, 3, 7, 9, 98, 88, 3, 1, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_ARG),
+                       ((one, one, 3, 7, 9, 96, 97, 3, 1, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_ARG),
+                       ((None, one, 3, 7, 9, 96, 88, 3, 1, _lib.UDP_F32, one, one, 1 << 20, None), UDP_ERR_ARG)):
+        assert L.udp_dwconvk_wgrad(*args) == code and L.udp_last_error(), args
 
 
 # ------------------------------------------------------------------ the parameter layout

@@ -26,7 +26,7 @@ DC_EXTRA = {"MODEL_SIZE": "1.0x", "DECONV_WITH_BIAS": False, "NUM_DECONV_LAYERS"
             "NUM_DECONV_KERNELS": [4, 4, 4], "FINAL_CONV_KERNEL": 1}
 # kernel-name fragment -> (label, bytes moved per launch as a function of the recorded grid is unknown: we time shapes
 # through the yardstick run instead)
-OURS = ("dw3_train_fwd_kernel", "dw3_dgrad_kernel", "dw3_wgrad_partial_kernel", "dw3_wgrad_reduce_kernel", "pixshuf2_train_kernel",
+OURS = ("dwk_fwd_kernel", "dwk_dgrad_kernel", "dwk_wgrad_partial_kernel", "dwk_wgrad_reduce_kernel", "pixshuf2_train_kernel",
         "shuffle_pair_fwd_kernel", "shuffle_pair_bwd_kernel", "chan_cat2_kernel", "chan_uncat2_kernel")
 
 

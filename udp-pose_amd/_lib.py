@@ -21,7 +21,7 @@ UDP_OP_SE_RES, UDP_OP_PRM_GATE, UDP_OP_PRM_DW9 = 20, 21, 22       # the gates of
 UDP_OP_SE_ACT = 23       # activation + squeeze-and-excitation with both biases: MobileNetV3 (csrc/dwconv.hip)
 UDP_ACT_NONE, UDP_ACT_RELU, UDP_ACT_HSWISH, UDP_ACT_SILU = 0, 1, 2, 4      # udp_conv_op.relu is an activation code (3: not assigned)
 UDP_BUF_NONE, UDP_BUF_OUTPUT = -1, -2
-ABI_VERSION = 19
+ABI_VERSION = 20
 MAX_LANES, MAX_WAIT = 4, 8
 
 
@@ -163,25 +163,23 @@ _SIGS = {
     "udp_maxpool3s2_fwd": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P]),
     "udp_maxpool3s2_bwd": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P]),
     "udp_stem7_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
-    # training of the ShuffleNetV2 pose nets: depthwise 3x3 forward / dgrad / wgrad, pixel shuffle, channel shuffle on
-    # pairs of halves, concat (csrc/shufflenet_train.hip)
-    "udp_dwconv3_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
-    "udp_dwconv3_dgrad": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P]),
-    "udp_dwconv3_wgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "udp_dwconv3_wgrad": (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P, C.c_size_t, _P]),
-    "udp_debug_dw_wgrad_plan": (C.c_int, [C.c_int] * 4 + [C.c_size_t, C.POINTER(C.c_int)]),
+    # the depthwise training convs of the ShuffleNetV2 and MobileNetV3 steps: 3x3 | 5x5 forward / dgrad / wgrad
+    # (csrc/dw_train.hip)
+    "udp_dwconvk_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P]),
+    "udp_dwconvk_dgrad": (C.c_int, [_P, _P] + [C.c_int] * 9 + [_P, _P]),
+    "udp_dwconvk_wgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "udp_dwconvk_wgrad": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P, C.c_size_t, _P]),
+    "udp_debug_dw_wgrad_plan": (C.c_int, [C.c_int] * 5 + [C.c_size_t, C.POINTER(C.c_int)]),
+    # training of the ShuffleNetV2 pose nets: pixel shuffle, channel shuffle on pairs of halves, concat
+    # (csrc/shufflenet_train.hip)
     "udp_pixshuf2_train_fwd": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P]),
     "udp_pixshuf2_train_bwd": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P]),
     "udp_shuffle_pair_fwd": (C.c_int, [_P, _P, C.c_int64] + [C.c_int] * 4 + [_P, _P, _P]),
     "udp_shuffle_pair_bwd": (C.c_int, [_P, _P, C.c_int64] + [C.c_int] * 4 + [_P, _P, _P]),
     "udp_chan_cat2": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "udp_chan_uncat2": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
-    # training of the MobileNetV3-small pose nets: depthwise 3x3 | 5x5 forward / dgrad / wgrad, hard-swish, squeeze-and-
-    # excitation with biases (csrc/mobilenetv3_train.hip)
-    "udp_dwconvk_train_fwd": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P]),
-    "udp_dwconvk_dgrad": (C.c_int, [_P, _P] + [C.c_int] * 9 + [_P, _P]),
-    "udp_dwconvk_wgrad_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "udp_dwconvk_wgrad": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P, C.c_size_t, _P]),
+    # training of the MobileNetV3-small pose nets: hard-swish, squeeze-and-excitation with biases
+    # (csrc/mobilenetv3_train.hip)
     "udp_hswish_fwd": (C.c_int, [_P, _P, C.c_int64, _P]),
     "udp_hswish_bwd": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "udp_se_train_fwd": (C.c_int, [_P] * 5 + [C.c_int] * 7 + [_P] * 5),

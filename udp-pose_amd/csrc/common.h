@@ -34,6 +34,21 @@ inline int fail(int code, const char* fmt, ...) {
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// workgroups of a grid-stride kernel: ceil(total / per), at least 1, at most cap
+inline unsigned blocks_for(long total, int per, long cap) {
+  long b = (total + per - 1) / per;
+  if (b < 1) b = 1;
+  return (unsigned)(b > cap ? cap : b);
+}
+// behind a <<<...>>> launch of entry point `who`
+inline int launched(const char* who) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(UDP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return UDP_OK;
+}
+
 // Split-fp16 ("f16x2") range guard.  fp16 tops out at 65504: a value of magnitude >= 65520 splits into hi = inf, and
 // the NaN that grows out of it downstream does not survive a ReLU (max(NaN, 0) = 0), so a finiteness test of the
 // final heat-maps can miss it.  Every kernel that WRITES split-fp16 values therefore raises this flag at the source

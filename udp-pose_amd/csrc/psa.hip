@@ -19,8 +19,6 @@
 
 namespace udp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // Split-fp16 storage (UDP_F16X2, csrc/conv.hip): per pixel the C hi values, then the C lo values (fp16),
 // x = hi + lo * 2^-11.
 struct H2 {};

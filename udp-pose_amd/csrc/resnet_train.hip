@@ -14,8 +14,6 @@
 
 namespace udp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---------------------------------------------------------------------------------------------
 // dx[n,iy,ix,ci] = sum_{co,ky,kx} dY[n, 2iy-1+ky, 2ix-1+kx, co] * w[ci][co][ky][kx]
 //
@@ -273,17 +271,6 @@ __global__ __launch_bounds__(256) void stem7_fwd_kernel(const float* __restrict_
     }
     *reinterpret_cast<f32x4*>(y + pix * kStemCout + 4 * q) = acc;
   }
-}
-
-static unsigned blocks_for(long total, int per, long cap) {
-  long b = (total + per - 1) / per;
-  if (b < 1) b = 1;
-  return (unsigned)(b > cap ? cap : b);
-}
-static int launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return UDP_OK;
 }
 
 }  // namespace udp

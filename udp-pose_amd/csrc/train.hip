@@ -20,8 +20,6 @@
 
 namespace udp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 template <typename T>
 __device__ __forceinline__ float tof(T v) {
   return (float)v;
@@ -799,11 +797,6 @@ static unsigned bn_blocks(long m, int c) {
   long nb = m / ((long)rg * 8);
   if (nb < 1) nb = 1;
   return (unsigned)(nb > kBnMaxBlocks ? kBnMaxBlocks : nb);
-}
-static int launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return UDP_OK;
 }
 
 }  // namespace udp

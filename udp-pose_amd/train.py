@@ -1118,10 +1118,7 @@ class ShuffleNetV2Trainer(Trainer):
         self._units = shufflenet_units(self.spec["model_size"])
         super().__init__(shapes, state_dict, num_joints, target_type, device=device, dtype=dtype, lr=lr, betas=betas, eps=eps,
                          bucket_elems=bucket_elems)
-        # one workspace for every depthwise weight gradient (they run in order on the side stream): the widest split
-        widest = max(_rup(s[0], 16) for k, s in shapes.items() if self._is_dw(k, s))
-        self._dw_ws = torch.empty(int(_lib.lib().udp_dwconv3_wgrad_workspace_bytes(256, 1, 1, widest)), dtype=torch.uint8,
-                                  device=self.device)
+        self._dw_ws = self._dw_workspace()
 
     def _head_shapes(self, num_joints, target_type):
         from .synth_shufflenet import shufflenet_param_shapes
@@ -1148,29 +1145,36 @@ class ShuffleNetV2Trainer(Trainer):
         return shape[0], shape[1], shape[2], False, key != "backbone.first_conv.0.weight"
 
     # ------------------------------------------------------------------ the ops the other nets do not have
+    def _dw_workspace(self):
+        """One workspace for every depthwise weight gradient (they run in order on the side stream): the widest split."""
+        L = _lib.lib()
+        return torch.empty(max(int(L.udp_dwconvk_wgrad_workspace_bytes(256, 1, 1, _rup(s[0], 16), s[2]))
+                               for k, s in self._shapes.items() if self._is_dw(k, s)), dtype=torch.uint8, device=self.device)
+
     def _dw(self, x, name, stride):
-        """Depthwise 3x3 (shufflenetv2.py:54, :66) straight from the parameter; its input gradient accumulates when the
-        input already has one (the input of a stride-2 unit feeds both branches)."""
+        """Depthwise conv (shufflenetv2.py:54, :66; the depthwise member of an InvertedResidual) straight from the
+        parameter, whose shape gives the kernel size; its input gradient accumulates when the input already has one (the
+        input of a stride-2 ShuffleNetV2 unit feeds both branches)."""
         L = _lib.lib()
         key = name + ".weight"
-        c_real = self._shapes[key][0]
+        c_real, ks = self._shapes[key][0], self._shapes[key][2]
         if x.c != c_real:
             raise ValueError("%s: expects %d channels, got %d" % (name, c_real, x.c))
         y = self._new(x.n, (x.h - 1) // stride + 1, (x.w - 1) // stride + 1, x.c)
-        _lib.check(L.udp_dwconv3_train_fwd(x.buf.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, stride, self._dt,
+        _lib.check(L.udp_dwconvk_train_fwd(x.buf.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, ks, stride, self._dt,
                                            y.buf.data_ptr(), self._stream()))
 
         def backward():
             dy = y.grad
-            self._on_side(lambda: _lib.check(L.udp_dwconv3_wgrad(
-                x.buf.data_ptr(), dy.data_ptr(), x.n, x.h, x.w, x.ck, c_real, stride, self._dt, self._g(key),
+            self._on_side(lambda: _lib.check(L.udp_dwconvk_wgrad(
+                x.buf.data_ptr(), dy.data_ptr(), x.n, x.h, x.w, x.ck, c_real, ks, stride, self._dt, self._g(key),
                 self._dw_ws.data_ptr(), self._dw_ws.numel(), self._stream())), dy, x.buf)
             if not x.needs_grad:
                 return
             have = x.grad is not None
             if not have:
                 x.grad = self._like(x)
-            _lib.check(L.udp_dwconv3_dgrad(dy.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, stride, int(have),
+            _lib.check(L.udp_dwconvk_dgrad(dy.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, ks, stride, int(have),
                                            self._dt, x.grad.data_ptr(), self._stream()))
         self._tape.append((y, backward, None, [key]))
         return y
@@ -1356,10 +1360,7 @@ class MobileNetV3Trainer(ShuffleNetV2Trainer):
         shapes = self._head_shapes(num_joints, target_type)
         Trainer.__init__(self, shapes, state_dict, num_joints, target_type, device=device, dtype=dtype, lr=lr, betas=betas,
                          eps=eps, bucket_elems=bucket_elems)
-        # one workspace for every depthwise weight gradient (they run in order on the side stream): the widest split
-        L = _lib.lib()
-        self._dw_ws = torch.empty(max(int(L.udp_dwconvk_wgrad_workspace_bytes(256, 1, 1, _rup(s[0], 16), s[2]))
-                                      for k, s in shapes.items() if self._is_dw(k, s)), dtype=torch.uint8, device=self.device)
+        self._dw_ws = self._dw_workspace()
 
     def _head_shapes(self, num_joints, target_type):
         from .synth_mobilenetv3 import mobilenetv3_ps_param_shapes
@@ -1383,33 +1384,6 @@ class MobileNetV3Trainer(ShuffleNetV2Trainer):
         return shape[0], shape[1], shape[2], False, key != "backbone.0.0.0.weight"
 
     # ------------------------------------------------------------------ the ops the other nets do not have
-    def _dwk(self, x, name, ks, stride):
-        """Depthwise ks x ks (the depthwise member of an InvertedResidual) straight from the parameter."""
-        L = _lib.lib()
-        key = name + ".weight"
-        c_real = self._shapes[key][0]
-        if x.c != c_real or self._shapes[key][2] != ks:
-            raise ValueError("%s: expects %d channels and a %dx%d kernel, got %d and %s" % (name, c_real, ks, ks, x.c, self._shapes[key]))
-        y = self._new(x.n, (x.h - 1) // stride + 1, (x.w - 1) // stride + 1, x.c)
-        _lib.check(L.udp_dwconvk_train_fwd(x.buf.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, ks, stride, self._dt,
-                                           y.buf.data_ptr(), self._stream()))
-
-        def backward():
-            dy = y.grad
-            wgrad = lambda: _lib.check(L.udp_dwconvk_wgrad(
-                x.buf.data_ptr(), dy.data_ptr(), x.n, x.h, x.w, x.ck, c_real, ks, stride, self._dt, self._g(key),
-                self._dw_ws.data_ptr(), self._dw_ws.numel(), self._stream()))
-            self._on_side(wgrad, dy, x.buf)
-            if not x.needs_grad:
-                return
-            have = x.grad is not None
-            if not have:
-                x.grad = self._like(x)
-            _lib.check(L.udp_dwconvk_dgrad(dy.data_ptr(), self._p(key), x.n, x.h, x.w, x.ck, c_real, ks, stride, int(have),
-                                           self._dt, x.grad.data_ptr(), self._stream()))
-        self._tape.append((y, backward, None, [key]))
-        return y
-
     def _hswish(self, x):
         """nn.Hardswish behind a BatchNorm that ran with relu=False; ``x`` stays on the tape for the derivative."""
         L = _lib.lib()
@@ -1465,10 +1439,7 @@ class MobileNetV3Trainer(ShuffleNetV2Trainer):
         if exp != cin:
             y = self._bn_act(self._conv(y, "%s.%d.0" % (p, m), bn_stats=True), "%s.%d.1" % (p, m), hs)
             m += 1
-        # 3x3 stays on ShuffleNetV2Trainer._dw (udp_dwconv3_*): the K = 3 arm of udp_dwconvk_* has no measurement on this
-        # code that shows it is not slower
-        dw = self._dw(y, "%s.%d.0" % (p, m), stride) if ks == 3 else self._dwk(y, "%s.%d.0" % (p, m), ks, stride)
-        y = self._bn_act(dw, "%s.%d.1" % (p, m), hs)
+        y = self._bn_act(self._dw(y, "%s.%d.0" % (p, m), stride), "%s.%d.1" % (p, m), hs)
         m += 1
         if se:
             y = self._se(y, "%s.%d" % (p, m))
