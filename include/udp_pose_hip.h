@@ -914,6 +914,65 @@ int udp_se_train_bwd(const void* dy, const void* x, const float* w1, const float
                      float* dw1, float* db1, float* dw2, float* db2, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Training of pose_mobilevitv2_pixel_shuffle (recipes experiments/coco/mobilevitv2/): what its backbone --
+ * deep_hrnet/lib/models/backbones/mobilevitv2.py, restated in tests/mobilevitv2_ref.py -- adds to a MobileNetV3 step
+ * (csrc/mobilevitv2_train.hip).  fp32 only (UDP_F32; anything else is UDP_ERR_UNSUPPORTED, "fp32 only").
+ *
+ * The conventions of the two sections above hold: NHWC tensors with a stored channel count that is a multiple of 4
+ * (the trainer stores ceil16 of the real count), real channels first; every stored channel of every output is written
+ * and the padded ones are exact zeros; no atomics, one summation order per shape (two runs, and eager and captured
+ * steps, are bit-equal); no host synchronisation and no allocation; every argument check comes before any launch.
+ * New symbols only, so UDP_POSE_ABI_VERSION stays as it is.
+ * ------------------------------------------------------------------------- */
+/* nn.SiLU (mobilevitv2.py:78-79, get_activation_fn 'swish') over `count` fp32 values, count a positive multiple of 4:
+ *   y = x * (1 / (1 + exp(-x)))  (the arithmetic of UDP_ACT_SILU);   dx = dy * s * (1 + x * (1 - s)), s = 1 / (1 + exp(-x))
+ * (x: the forward's INPUT).  Finite for every finite x: where exp(-x) overflows s is 0 (y = -0, dx = 0), where it
+ * underflows s is 1 (y = x, dx = dy).  0 maps to 0, so pads stay zero. */
+int udp_silu_fwd(const void* x, void* y, int64_t count, void* stream);
+int udp_silu_bwd(const void* dy, const void* x, void* dx, int64_t count, void* stream);
+/* GroupNorm(num_groups = 1, C) under model.train() -- "layer_norm_2d", mobilevitv2.py:139-140 (pre_norm_attn.0,
+ * pre_norm_ffn.0 of every LinearAttnFFN :779-817 and the block's last norm :932-934).  x, y: [n,h,w,ck]; gamma, beta:
+ * c_real floats.  Per image over its c_real*h*w REAL elements (pads are not counted):
+ *   mu = mean(x)   r = 1 / sqrt(mean((x - mu)^2) + eps)   y = (x - mu) * r * gamma[c] + beta[c]   (pads of y: 0)
+ * save: [n][2] = (mu, r).  The statistics are shifted sums in fp64, sum(x - x0) and sum((x - x0)^2) with x0 the image's
+ * first element, so a map whose mean is 1000 x its standard deviation keeps its variance.  An image's pixels are cut
+ * into `split` runs of consecutive pixels, one workgroup each, split = udp_gnorm_train_split(h, w, ck): a pure function
+ * of the shape (a run holds at least 1024 16-byte channel groups, at most 64 runs); the runs' partial sums go through the
+ * workspace and are added in index order.  Two launches.  workspace: udp_gnorm_train_workspace_bytes(n, h, w, ck) =
+ * n * split * (16 + 8 ck) bytes, for the forward and the backward alike (0: bad shape); less is UDP_ERR_WORKSPACE. */
+int udp_gnorm_train_split(int h, int w, int ck);
+size_t udp_gnorm_train_workspace_bytes(int n, int h, int w, int ck);
+int udp_gnorm_train_fwd(const void* x, const float* gamma, const float* beta, int n, int h, int w, int ck, int c_real,
+                        int dtype, float eps, void* y, float* save, void* workspace, size_t workspace_bytes, void* stream);
+/* Its backward (autograd through F.group_norm), with g^ = dy * gamma[c] and x^ = (x - mu) * r:
+ *   dx (+)= r * (g^ - mean(g^) - x^ * mean(g^ x^))      (means over the image's real elements; pads of dx: 0)
+ *   dgamma[c] = sum_{n,h,w} dy x^     dbeta[c] = sum_{n,h,w} dy      (c < c_real only; overwritten)
+ * `accumulate` != 0 adds into an existing dx (the input of every GroupNorm also feeds the residual).  Three launches:
+ * per run the two image sums (fp64) and the per-channel sums (fp32, the run's pixels in a fixed order), the dx pass,
+ * and dgamma / dbeta = the (image, run) partials added in index order. */
+int udp_gnorm_train_bwd(const void* dy, const void* x, const float* gamma, const float* save, int n, int h, int w, int ck,
+                        int c_real, int dtype, int accumulate, void* dx, float* dgamma, float* dbeta, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* The separable ("linear") self-attention core between qkv_proj and out_proj under model.train():
+ * LinearSelfAttention._forward_self_attn, mobilevitv2.py:671-689, in the map form of
+ * tests/mobilevitv2_ref.py:linear_attention_core -- the four patch positions are the parity classes (y & 1, x & 1) of
+ * the map, M = h*w/4 pixels each, in row-major order of the (h/2, w/2) grid.  qkv: [n,h,w,ck_qkv], the qkv conv's
+ * output in the PARAMETER's channel order (channel 0 the query, 1..d the keys, d+1..2d the values; not the key | value
+ * | query order of the packed inference weights), ck_qkv = ceil16(1 + 2d).  Per image and class:
+ *   s_i = softmax_i(q_i) (maximum subtracted)   ctx[c] = sum_i s_i k_ic   out_ic = relu(v_ic) * ctx[c]
+ * out: [n,h,w,ck_out], ck_out >= d, channels d.. zero.  Kept for the backward: scores [n][4][M], ctx [n][4][d]
+ * (class = (y & 1) * 2 + (x & 1)).  One launch, a workgroup per (image, class).  h and w even, d % 16 == 0, d <= 512,
+ * M <= 2048: otherwise UDP_ERR_UNSUPPORTED; ck_qkv or ck_out that do not fit d: UDP_ERR_ARG. */
+int udp_linattn_train_fwd(const void* qkv, int n, int h, int w, int ck_qkv, int d, int dtype, void* out, int ck_out,
+                          float* scores, float* ctx, void* stream);
+/* Its backward, g = dout:
+ *   dv_ic = g_ic ctx[c] [v_ic > 0]  (0 at v = 0, torch's rule)    dctx[c] = sum_i g_ic relu(v_ic)    dk_ic = s_i dctx[c]
+ *   e_i = sum_c k_ic dctx[c]        dq_i = s_i (e_i - sum_j s_j e_j)
+ * All ck_qkv channels of dqkv [n,h,w,ck_qkv] are written, the pads as zero (qkv has one consumer: nothing accumulates). */
+int udp_linattn_train_bwd(const void* dout, const void* qkv, const float* scores, const float* ctx, int n, int h, int w,
+                          int ck_qkv, int d, int ck_out, int dtype, void* dqkv, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Training of the polarized self-attention block of pose_hrnet_psa.  Replaces
  * PSA_s.forward (deep_hrnet/lib/models/PSA.py:190-269: spatial_pool :190-222,
  * channel_pool :224-258) under model.train() and its autograd backward.

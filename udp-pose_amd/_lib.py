@@ -185,6 +185,15 @@ _SIGS = {
     "udp_se_train_fwd": (C.c_int, [_P] * 5 + [C.c_int] * 7 + [_P] * 5),
     "udp_se_train_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "udp_se_train_bwd": (C.c_int, [_P] * 7 + [C.c_int] * 8 + [_P] * 6 + [C.c_size_t, _P]),
+    # training of pose_mobilevitv2_pixel_shuffle: SiLU, GroupNorm(1, C), the separable self-attention core
+    "udp_silu_fwd": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "udp_silu_bwd": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "udp_gnorm_train_split": (C.c_int, [C.c_int] * 3),
+    "udp_gnorm_train_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "udp_gnorm_train_fwd": (C.c_int, [_P] * 3 + [C.c_int] * 6 + [C.c_float] + [_P] * 3 + [C.c_size_t, _P]),
+    "udp_gnorm_train_bwd": (C.c_int, [_P] * 4 + [C.c_int] * 7 + [_P] * 4 + [C.c_size_t, _P]),
+    "udp_linattn_train_fwd": (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_int] + [_P] * 3),
+    "udp_linattn_train_bwd": (C.c_int, [_P] * 4 + [C.c_int] * 7 + [_P] * 2),
     # training of the polarized self-attention block (pose_hrnet_psa)
     "udp_psa_train_save_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "udp_psa_train_fwd_pool": (C.c_int, [C.POINTER(PsaTrainArgs), C.c_int, _P]),

@@ -70,7 +70,8 @@ class PoseNetHip:
 
     def trainer(self):
         raise NotImplementedError("%s: the training step covers pose_hrnet, pose_hrnet_psa, pose_resnet, the two "
-                                  "ShuffleNetV2 nets and the two MobileNetV3-small nets only" % self.NAME)
+                                  "ShuffleNetV2 nets, the two MobileNetV3-small nets and pose_mobilevitv2_pixel_shuffle only"
+                                  % self.NAME)
 
     def to(self, device):
         self.device = torch.device(device)
@@ -699,18 +700,23 @@ def get_pose_net_shufflenetv2_plus(cfg, is_train, **kwargs):
     return PoseShuffleNetV2PlusHip(cfg, **kwargs)
 
 
-class PoseMobileViTv2Hip(PoseNetHip):
+class PoseMobileViTv2Hip(_Trainable, PoseNetHip):
     """pose_mobilevitv2_pixel_shuffle (deep_hrnet/lib/models/pose_mobilevitv2_pixel_shuffle.py:23-60: the MobileViTv2
     0.5 / 0.75 / 1.0 backbone -- MobileNetV2 blocks with SiLU, GroupNorm(1, C) and separable self-attention on 2x2
-    patches --, the pixel-shuffle (DUC) decoder, ``final_layer``) inference through the same C ABI; ``state_dict`` in
+    patches --, the pixel-shuffle (DUC) decoder, ``final_layer``) through the same C ABI; ``state_dict`` in
     the reference module's key format (``backbone.classifier`` is accepted and unused, as in the reference's forward).
     The width comes from MODEL.EXTRA.MODEL_SIZE; MODEL.CONFIG (the reference's second YAML) is accepted and ignored.
-    Storage modes "f32" and "f16x2"; input height and width must be multiples of 64."""
+    Storage modes "f32" and "f16x2"; input height and width must be multiples of 64.  ``trainable`` (what
+    ``MODELS[NAME](cfg, is_train=True)`` sets): the model also has the training surface of ``PoseShuffleNetV2Hip`` --
+    ``init_weights``, ``train()``, ``parameters()``, ``trainer()`` (a train.MobileViTv2Trainer, fp32 whatever the storage
+    mode of the inference program)."""
 
     NAME = "pose_mobilevitv2_pixel_shuffle"
     DTYPES = ("f32", "f16x2")
+    TRAINS = True                # a net of this class can be built trainable
+    TRAINER = "MobileViTv2Trainer"
 
-    def __init__(self, cfg, dtype="f32"):
+    def __init__(self, cfg, dtype="f32", trainable=False):
         from .mobilevitv2_plan import mobilevitv2_spec
         if dtype not in self.DTYPES:
             raise NotImplementedError("%s: dtype %r is not supported; supported modes: %s" % (self.NAME, dtype, ", ".join(self.DTYPES)))
@@ -719,6 +725,7 @@ class PoseMobileViTv2Hip(PoseNetHip):
         self.num_joints = int(_get(cfg, "MODEL", "NUM_JOINTS"))
         self.target_type = _get(cfg, "MODEL", "TARGET_TYPE")
         self.spec = mobilevitv2_spec(self.extra, self.num_joints, self.target_type)   # NotImplementedError for an unknown size ...
+        self.trainable = bool(trainable) and self.TRAINS
 
     def param_shapes(self):
         from .synth_mobilevitv2 import mobilevitv2_param_shapes
@@ -728,7 +735,70 @@ class PoseMobileViTv2Hip(PoseNetHip):
                                         final_kernel=sp["final_kernel"])
 
     def init_weights(self, pretrained=""):
-        raise NotImplementedError("%s: training (and its weight initialisation) is out of scope; load a state_dict" % self.NAME)
+        """What the reference's constructor leaves behind (the pose module has no ``init_weights`` of its own).  The
+        backbone is ``MobileViTv2.reset_parameters`` = ``initialize_weights`` (backbones/utils/init_utils.py:218-235) under
+        backbones/configs/mobilevitv2-*.yaml, which set no ``model.layer.conv_init`` / ``linear_init``: every nn.Conv2d --
+        depthwise, qkv_proj, out_proj and the FFN included -- ``kaiming_normal_(mode="fan_out")`` = N(0, 2 / (shape[0] k k))
+        with a zero bias, every BatchNorm and GroupNorm weight 1 / bias 0, the classifier's LinearLayer N(0, 0.01) with a
+        zero bias.  Decoder / ``final_layer`` keep torch's nn.Conv2d / BatchNorm2d defaults, as in
+        ``PoseShuffleNetV2Hip.init_weights``.  A ``pretrained`` that names a local file is read by the rules of the
+        reference's ``load_pretrained_model`` (backbones/mobilevitv2.py:55-64): ``torch.load`` gives a bare state_dict
+        with the backbone's own keys (no ``backbone.`` prefix) that is loaded STRICTLY -- a missing, unexpected or
+        differently sized tensor is a RuntimeError.  Any other truthy value is a FileNotFoundError (the reference logs
+        the path and fails in ``torch.load``); nothing is ever downloaded.  Draws come from torch's global generator."""
+        import math
+        import os
+        if not self.trainable:
+            raise NotImplementedError("%s: built with is_train=False (inference only); load a state_dict" % self.NAME)
+        shapes = self.param_shapes()
+        sd = {}
+        for k, shape in shapes.items():
+            backbone = k.startswith("backbone.")
+            if k.endswith("num_batches_tracked"):
+                sd[k] = torch.zeros((), dtype=torch.int64)
+            elif k.endswith("running_var"):
+                sd[k] = torch.ones(shape)
+            elif k.endswith("running_mean"):
+                sd[k] = torch.zeros(shape)
+            elif backbone and len(shape) == 4:
+                sd[k] = torch.randn(shape) * math.sqrt(2.0 / (shape[0] * shape[2] * shape[3]))
+            elif backbone and len(shape) == 2:
+                sd[k] = torch.randn(shape) * 0.01             # the classifier's LinearLayer
+            elif backbone:                                    # 1-d: a norm's weight / bias, or the bias of a conv / the classifier
+                norm = k.endswith(".weight")                  # (no conv or linear weight is 1-d)
+                sd[k] = torch.ones(shape) if norm else torch.zeros(shape)
+            elif (k.rsplit(".", 1)[0] + ".running_mean") in shapes:
+                sd[k] = torch.ones(shape) if k.endswith(".weight") else torch.zeros(shape)
+            else:                                             # nn.Conv2d defaults, weight before bias
+                w = shapes[k.rsplit(".", 1)[0] + ".weight"]
+                bound = 1.0 / math.sqrt(w[1] * w[2] * w[3])
+                sd[k] = (torch.rand(shape) * 2 - 1) * bound
+        if pretrained:
+            if not (isinstance(pretrained, str) and os.path.isfile(pretrained)):
+                raise FileNotFoundError("%s: MODEL.PRETRAINED=%r is not a local file (nothing is downloaded)" % (self.NAME, pretrained))
+            wts = torch.load(pretrained, map_location="cpu", weights_only=True)
+            want = [k[len("backbone."):] for k in shapes if k.startswith("backbone.")]
+            missing = [k for k in want if k not in wts and not k.endswith("num_batches_tracked")]
+            unexpected = [k for k in wts if k not in want]
+            if missing or unexpected:
+                raise RuntimeError("%s: pretrained backbone state_dict mismatch: missing %s unexpected %s"
+                                   % (self.NAME, missing[:5], unexpected[:5]))
+            for k, v in wts.items():
+                if tuple(v.shape) != tuple(shapes["backbone." + k]):
+                    raise RuntimeError("%s: size mismatch for %s: %s vs %s" % (self.NAME, k, tuple(v.shape), tuple(shapes["backbone." + k])))
+                sd["backbone." + k] = v
+        return self._set_weights(sd)
+
+    def trainer(self):
+        if not self.trainable:
+            raise NotImplementedError("%s: built with is_train=False (inference only); MODELS[%r](cfg, is_train=True) "
+                                      "returns the trainable model" % (self.NAME, self.NAME))
+        return super().trainer()
+
+    def _make_trainer(self):
+        from . import train
+        return getattr(train, self.TRAINER)(self.spec, self.num_joints, self.target_type, self._sd, device=self.device,
+                                            dtype="f32")
 
     def _make_program(self, h, w):
         from .mobilevitv2_plan import MobileViTv2Program
@@ -736,9 +806,10 @@ class PoseMobileViTv2Hip(PoseNetHip):
 
 
 def get_pose_net_mobilevitv2(cfg, is_train, **kwargs):
-    """pose_mobilevitv2_pixel_shuffle.py:63-72 (``get_pose_net``); inference only -- the weights come from
+    """pose_mobilevitv2_pixel_shuffle.py:63-72 (``get_pose_net``): trainable under ``is_train``
+    (``init_weights(cfg.MODEL.PRETRAINED)`` when cfg.MODEL.INIT_WEIGHTS says so); otherwise the weights come from
     ``load_state_dict``."""
-    return PoseMobileViTv2Hip(cfg, **kwargs)
+    return _init_under_is_train(PoseMobileViTv2Hip(cfg, trainable=bool(is_train), **kwargs), cfg, is_train)
 
 
 class PoseMobileViTHip(PoseNetHip):

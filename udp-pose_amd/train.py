@@ -6,7 +6,8 @@ of the train-mode forward its subclass runs op by op through the C ABI, walks it
 (``loss.backward()``), then ``udp_adam_step`` (``optimizer.step()``).  ``HRNetTrainer`` is the graph of
 lib/models/pose_hrnet.py:436-471 (and pose_hrnet_psa), ``PoseResNetTrainer`` that of lib/models/pose_resnet.py:195-209,
 ``ShuffleNetV2Trainer`` / ``ShuffleNetV2DeconvTrainer`` those of the two ShuffleNetV2 pose nets, ``MobileNetV3Trainer`` /
-``MobileNetV3DeconvTrainer`` those of the two MobileNetV3-small pose nets.
+``MobileNetV3DeconvTrainer`` those of the two MobileNetV3-small pose nets, ``MobileViTv2Trainer`` that of
+pose_mobilevitv2_pixel_shuffle.
 torch is used for device memory only; every arithmetic step is a kernel of libudp_pose_hip.so.
 
 Reference contract mirrored: ``JointsMSELoss`` / ``JointsMSELoss_offset`` (lib/core/loss.py),
@@ -250,7 +251,9 @@ class Trainer:
         op.out_buf = _lib.UDP_BUF_OUTPUT if nchw else 0
         return op
 
-    def _conv(self, x, name, stride=1, bias_key=None, nchw_out=False, bn_stats=False, slot=0):
+    def _conv(self, x, name, stride=1, bias_key=None, nchw_out=False, bn_stats=False, slot=0, res=None):
+        """``res``: an activation of the output's shape added in the conv's epilogue (y = conv(x) + bias + res, the
+        residual pointer of udp_conv2d_fused); the backward hands dy on to ``res.grad``, as ``_bn`` does for its ``res``."""
         L = _lib.lib()
         bn_ws = self._bn_wss[slot]
         cout, cin, ks, wf, wd = self._convs[name]
@@ -273,6 +276,8 @@ class Trainer:
             y_keep = b
         else:
             y_keep = None
+        if res is not None and (nchw_out or bn_stats or (res.n, res.h, res.w, res.ck) != (y.n, y.h, y.w, y.ck)):
+            raise ValueError("%s: a residual needs an NHWC output of its own shape and no fused BatchNorm statistics" % name)
         if bn_stats and self.fuse_bn_stats and not nchw_out and (y.c == y.ck or self.bn_over_stored):
             # the BatchNorm that follows reads its statistics from the conv epilogue's partial sums
             rows = C.c_int(0)
@@ -287,11 +292,18 @@ class Trainer:
                 y.bn_rows = rows.value
                 y.bn_ws = bn_ws
         else:
-            _lib.check(L.udp_conv2d_fused(C.byref(op), self._dt, x.n, x.buf.data_ptr(), wf.data_ptr(), bias, None, None,
-                                          None, None, y.buf.data_ptr(), self._stream()))
+            _lib.check(L.udp_conv2d_fused(C.byref(op), self._dt, x.n, x.buf.data_ptr(), wf.data_ptr(), bias,
+                                          None if res is None else res.buf.data_ptr(), None, None, None, y.buf.data_ptr(),
+                                          self._stream()))
 
         def backward():
             dy = y.grad                                   # NHWC [n,ho,wo,ck(cout)]
+            if res is not None and res.needs_grad:        # a copy: the side stream still reads dy when res.grad is added to
+                have = res.grad is not None
+                if not have:
+                    res.grad = self._like(res)
+                _lib.check(L.udp_ew_accumulate(res.grad.data_ptr(), dy.data_ptr(), res.n, res.h, res.w, res.ck, 0,
+                                               int(not have), 0, self._dt, self._stream()))
 
             def wgrad():
                 _lib.check(L.udp_conv2d_wgrad(x.buf.data_ptr(), dy.data_ptr(), x.n, x.h, x.w, x.ck, ho, wo, y.ck, ks,
@@ -317,11 +329,11 @@ class Trainer:
                     stuffed = 1
             dop = self._conv_op(ks, 1, y.ck, x.ck, hh, ww, x.h, x.w)
             dop.in_stuff2 = stuffed
-            res = x.grad
-            if res is None:
+            acc = x.grad
+            if acc is None:
                 x.grad = self._like(x)
             _lib.check(L.udp_conv2d_fused(C.byref(dop), self._dt, x.n, src.data_ptr(), wd.data_ptr(),
-                                          self._zeros.data_ptr(), None if res is None else res.data_ptr(), None, None,
+                                          self._zeros.data_ptr(), None if acc is None else acc.data_ptr(), None, None,
                                           None, x.grad.data_ptr(), self._stream()))
         self._tape.append((y, backward, y_keep, [name + ".weight"] + ([bias_key] if bias_key else [])))
         return y
@@ -1485,3 +1497,170 @@ class MobileNetV3DeconvTrainer(MobileNetV3Trainer):
                                                deconv_with_bias=sp["deconv_with_bias"])
 
     _head = ShuffleNetV2DeconvTrainer._head
+
+
+class MobileViTv2Trainer(ShuffleNetV2Trainer):
+    """pose_mobilevitv2_pixel_shuffle (deep_hrnet/lib/models/pose_mobilevitv2_pixel_shuffle.py:23-60; recipes
+    experiments/coco/mobilevitv2/mobilevitv2-{0.5,0.75,1.0}_256x192_adam_lr1e-3_pixel_shuffle.yaml) on the base step.
+    ``spec``: the dict of ``mobilevitv2_plan.mobilevitv2_spec``.  The graph is tests/mobilevitv2_ref.py's, op for op, in
+    train mode; it is deterministic -- the backbone YAMLs set no dropout (backbones/mobilevitv2.py:1340-1357).  The
+    backbone's BatchNorms are nn.BatchNorm2d(momentum=0.1) with the default eps 1e-5 (get_normalization_layer :115-120,
+    ``model.normalization.momentum`` of backbones/configs/mobilevitv2-*.yaml): ``_bn``'s defaults.  fp32 only: the
+    reference's precision, and the depthwise, GroupNorm and attention kernels have no bf16 form.
+
+    What it takes from ``ShuffleNetV2Trainer``: the padded layout (``_key_stride``, ``bn_over_stored`` -- the 0.75 width
+    has 24- and 48-channel tensors, and every qkv map has 1 + 2d channels), ``_dw`` for every [C][1][3][3] weight,
+    ``_pixshuf`` and the head.  The qkv map keeps the PARAMETER's channel order (query | keys | values), so the weight
+    gradient lands in the parameter layout.  ``backbone.classifier.1.*`` are parameters the forward never applies
+    (:1440-1444): their gradient stays zero."""
+
+    NAME = "pose_mobilevitv2_pixel_shuffle"
+    GN_EPS = 1e-5                        # nn.GroupNorm's default (:139-140 passes none)
+
+    def __init__(self, spec, num_joints, target_type, state_dict, device="cuda", dtype="f32", lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-8, bucket_elems=6 * 1024 * 1024):
+        if dtype != "f32":
+            raise ValueError("%s trains in fp32 only (dtype %r): the depthwise, GroupNorm and attention kernels have no bf16 "
+                             "form" % (self.NAME, dtype))
+        self.spec = dict(spec)
+        shapes = self._head_shapes(num_joints, target_type)
+        Trainer.__init__(self, shapes, state_dict, num_joints, target_type, device=device, dtype=dtype, lr=lr, betas=betas,
+                         eps=eps, bucket_elems=bucket_elems)
+        self._dw_ws = self._dw_workspace()
+
+    def _head_shapes(self, num_joints, target_type):
+        from .synth_mobilevitv2 import mobilevitv2_param_shapes
+        sp = self.spec
+        if any(a % 64 for a in sp["architecture"]):
+            raise ValueError("%s trainer: ARCHITECTURE=%s -- the pixel shuffle moves 16 input channels per thread, every entry "
+                             "must be a multiple of 64" % (self.NAME, tuple(sp["architecture"])))
+        return mobilevitv2_param_shapes(model_size=sp["model_size"], num_joints=int(num_joints), target_type=target_type,
+                                        start_channels=sp["start_channels"], architecture=tuple(sp["architecture"]),
+                                        final_kernel=sp["final_kernel"])
+
+    @staticmethod
+    def _is_dw(key, shape):
+        return len(shape) == 4 and shape[1] == 1 and shape[2] == 3 and key.startswith("backbone.")
+
+    def _conv_entry(self, key, shape):
+        if self._is_dw(key, shape):
+            return None                     # the depthwise kernels read the parameter as it is
+        return shape[0], shape[1], shape[2], False, key != "backbone.conv_1.block.conv.weight"
+
+    # ------------------------------------------------------------------ the ops the other nets do not have
+    def _silu(self, x):
+        """nn.SiLU behind a BatchNorm that ran with relu=False, or behind a biased conv; ``x`` stays on the tape for the
+        derivative."""
+        L = _lib.lib()
+        y = self._new(x.n, x.h, x.w, x.c)
+        _lib.check(L.udp_silu_fwd(x.buf.data_ptr(), y.buf.data_ptr(), x.buf.numel(), self._stream()))
+
+        def backward():
+            self._one_consumer("SiLU", x)
+            x.grad = self._like(x)
+            _lib.check(L.udp_silu_bwd(y.grad.data_ptr(), x.buf.data_ptr(), x.grad.data_ptr(), x.buf.numel(), self._stream()))
+        self._tape.append((y, backward, None, []))
+        return y
+
+    def _gnorm(self, x, name):
+        """GroupNorm(1, C) ``name`` in train mode; its input gradient accumulates when the input already has one (the
+        input of every GroupNorm of a LinearAttnFFN also feeds the residual)."""
+        L = _lib.lib()
+        keys = [name + ".weight", name + ".bias"]
+        if tuple(self._shapes[keys[0]]) != (x.c,):
+            raise ValueError("%s: GroupNorm over %d channels, weight %s" % (name, x.c, self._shapes[keys[0]]))
+        y = self._new(x.n, x.h, x.w, x.c)
+        save = torch.empty(2 * x.n, dtype=torch.float32, device=self.device)
+        nbytes = int(L.udp_gnorm_train_workspace_bytes(x.n, x.h, x.w, x.ck))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _lib.check(L.udp_gnorm_train_fwd(x.buf.data_ptr(), self._p(keys[0]), self._p(keys[1]), x.n, x.h, x.w, x.ck, x.c, self._dt,
+                                         self.GN_EPS, y.buf.data_ptr(), save.data_ptr(), ws.data_ptr(), nbytes, self._stream()))
+
+        def backward():
+            have = x.grad is not None
+            if not have:
+                x.grad = self._like(x)
+            bws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(L.udp_gnorm_train_bwd(y.grad.data_ptr(), x.buf.data_ptr(), self._p(keys[0]), save.data_ptr(), x.n, x.h,
+                                             x.w, x.ck, x.c, self._dt, int(have), x.grad.data_ptr(), self._g(keys[0]),
+                                             self._g(keys[1]), bws.data_ptr(), nbytes, self._stream()))
+        self._tape.append((y, backward, save, keys))
+        return y
+
+    def _linattn(self, qkv, d):
+        """The separable self-attention core between qkv_proj and out_proj (mobilevitv2.py:671-689) on the qkv map."""
+        L = _lib.lib()
+        if qkv.c != 1 + 2 * d:
+            raise ValueError("linear attention: a qkv map of %d channels for d = %d" % (qkv.c, d))
+        y = self._new(qkv.n, qkv.h, qkv.w, d)
+        m = qkv.h * qkv.w // 4
+        scores = torch.empty(qkv.n * 4 * m, dtype=torch.float32, device=self.device)
+        ctx = torch.empty(qkv.n * 4 * d, dtype=torch.float32, device=self.device)
+        _lib.check(L.udp_linattn_train_fwd(qkv.buf.data_ptr(), qkv.n, qkv.h, qkv.w, qkv.ck, d, self._dt, y.buf.data_ptr(), y.ck,
+                                           scores.data_ptr(), ctx.data_ptr(), self._stream()))
+
+        def backward():
+            self._one_consumer("linear attention", qkv)
+            qkv.grad = self._like(qkv)
+            _lib.check(L.udp_linattn_train_bwd(y.grad.data_ptr(), qkv.buf.data_ptr(), scores.data_ptr(), ctx.data_ptr(), qkv.n,
+                                               qkv.h, qkv.w, qkv.ck, d, y.ck, self._dt, qkv.grad.data_ptr(), self._stream()))
+        self._tape.append((y, backward, (scores, ctx), []))
+        return y
+
+    # ------------------------------------------------------------------ the graph (tests/mobilevitv2_ref.py)
+    def _cbn(self, x, name, act, stride=1, dw=False, res=None):
+        """ConvLayer with a norm (:321-345): conv or depthwise conv, BatchNorm, SiLU when ``act``."""
+        if dw:
+            y = self._dw(x, name + ".block.conv", stride)
+        else:
+            y = self._conv(x, name + ".block.conv", stride=stride, bn_stats=True)
+        y = self._bn(y, name + ".block.norm", relu=False, res=res)
+        return self._silu(y) if act else y
+
+    def _inverted_residual(self, x, p, stride):
+        """InvertedResidual.forward (:226-230); the shortcut is the ``res`` of the red_1x1 BatchNorm."""
+        y = self._cbn(x, p + ".block.exp_1x1", True)
+        y = self._cbn(y, p + ".block.conv_3x3", True, stride=stride, dw=True)
+        cout = self._shapes[p + ".block.red_1x1.block.conv.weight"][0]
+        return self._cbn(y, p + ".block.red_1x1", False, res=x if stride == 1 and x.c == cout else None)
+
+    def _biased(self, x, name, res=None):
+        return self._conv(x, name + ".block.conv", bias_key=name + ".block.conv.bias", res=res)
+
+    def _mit_block(self, x, q):
+        """MobileViTBlockv2.forward_spatial (:1105-1126), map form."""
+        t = self._cbn(x, q + ".local_rep.0", True, dw=True)
+        t = self._conv(t, q + ".local_rep.1.block.conv")
+        d, u = t.c, 0
+        while ("%s.global_rep.%d.pre_norm_attn.0.weight" % (q, u)) in self._shapes:            # LinearAttnFFN.forward (:839-855)
+            g = "%s.global_rep.%d" % (q, u)
+            qkv = self._biased(self._gnorm(t, g + ".pre_norm_attn.0"), g + ".pre_norm_attn.1.qkv_proj")
+            t = self._biased(self._linattn(qkv, d), g + ".pre_norm_attn.1.out_proj", res=t)
+            f = self._silu(self._biased(self._gnorm(t, g + ".pre_norm_ffn.0"), g + ".pre_norm_ffn.1"))
+            t = self._biased(f, g + ".pre_norm_ffn.3", res=t)
+            u += 1
+        t = self._gnorm(t, "%s.global_rep.%d" % (q, u))
+        return self._cbn(t, q + ".conv_proj", False)
+
+    def forward(self, x):
+        """Train-mode forward.  x: fp32 [N,3,H,W] on the device.  Returns fp32 [N,C,H/4,W/4]."""
+        L = _lib.lib()
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+            raise ValueError("expected contiguous fp32 [N,3,H,W]")
+        n, _, h, w = x.shape
+        if h % 64 or w % 64:
+            raise ValueError("input %dx%d must be a multiple of 64 (2x2 patches on the 1/32 map)" % (h, w))
+        self._tape = []
+        _lib.check(L.udp_pack_conv_weights_batch(self._pack_table.data_ptr(), len(self._convs), self._dt, self._stream()))
+        a = self._new(n, h, w, 3, needs_grad=False)
+        _lib.check(L.udp_nchw_to_nhwc(x.data_ptr(), n, 3, h, w, a.ck, a.buf.data_ptr(), self._dt, self._stream()))
+        a = self._cbn(a, "backbone.conv_1", True, stride=2)                                     # :1198-1206
+        a = self._inverted_residual(a, "backbone.layer_1.0", 1)
+        a = self._inverted_residual(a, "backbone.layer_2.0", 2)
+        a = self._inverted_residual(a, "backbone.layer_2.1", 1)
+        for layer in (3, 4, 5):                                                                 # :1313-1366
+            a = self._inverted_residual(a, "backbone.layer_%d.0" % layer, 2)
+            a = self._mit_block(a, "backbone.layer_%d.1" % layer)
+        a = self._head(a)
+        self._out = self._conv(a, "final_layer", bias_key="final_layer.bias", nchw_out=True)
+        return self._out.buf
